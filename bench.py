@@ -15,8 +15,15 @@ Other configs of BASELINE.json (same contract, same timing bracket):
 ``--model resnet50`` (config 3: ResNet-50 224x224 bf16 DDP, images/s) and
 ``--model llama3-8b`` (config 4: Llama-3-8B bf16 DDP, tokens/s + MFU).
 
+A plain run sets up, warms up, times exactly K steps and prints the result
+line.  ``--full`` adds the second half of the BASELINE metric, submit ->
+first optimizer step through the whole operator stack, measured after the
+timed steps.  ``--dump-outputs DIR`` writes what the last timed step left
+(parameters, momentum, loss) as ``.npy`` files, to compare two builds.
+
 Usage:  python bench.py [--gpus N] [--steps K] [--warmup W] [--impl fused|eager]
                         [--model mnist|resnet50|llama3-8b|llama3-1b]
+                        [--full] [--dump-outputs DIR]
 """
 from __future__ import annotations
 
@@ -54,9 +61,17 @@ def parse_args(argv=None):
                    help="DistributedSampler semantics: one dataset, disjoint per-rank shards (true global "
                         "throughput); default: every rank its own stream (reference-equivalent, no sampler)")
     p.add_argument("--cpu", action="store_true", help="run on CPU with gloo (debug only)")
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps also measure submit -> first optimizer step through the whole "
+                        "operator stack (a run of its own, outside the timed region); a plain run only sets "
+                        "up, warms up, times the steps and prints the result line")
     p.add_argument("--no-latency", action="store_true",
-                   help="skip the submit -> first-step measurement (default: measured at world size 1, after "
-                        "the throughput run, through the whole operator stack)")
+                   help="with --full: skip the submit -> first-step measurement")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps write what the last step left (parameters, optimizer momentum, "
+                        "per-sample loss) as DIR/<name>.npy, float32, at most 64 MB in all (a fixed seeded "
+                        "sample of a larger array); same arguments, same inputs, so two builds compare "
+                        "output for output")
     p.add_argument("--force-ddp", action="store_true",
                    help="large models at --gpus 1: the whole DDP path (flat buckets, comm stream, per-bucket "
                         "collectives over a 1-rank RCCL group, xGMI hook) -- its cost on one GPU")
@@ -254,6 +269,9 @@ def main(argv=None):
             raise SystemExit(f"[bench] the RCCL schedule failed too: {again}")
     run = None
     loss = trainer.last_loss()
+    if args.dump_outputs and env.rank == 0:
+        print(f"[bench] outputs of the last step -> {args.dump_outputs}: {dump_outputs(args.dump_outputs, trainer)}",
+              file=sys.stderr)
     # evidence of the world that was measured (outside the timed region):
     # the ranks, their devices and transports, and whether the replicas
     # still hold bit-identical parameters after the timed steps
@@ -303,8 +321,8 @@ def main(argv=None):
         if identical is not None:
             out["ranks_bit_identical"] = identical
     pdist.cleanup()
-    if out is not None and not args.no_latency and os.environ.get("BENCH_LATENCY", "1") == "1":
-        # second half of the BASELINE metric, outside the timed region, on
+    if out is not None and args.full and not args.no_latency and os.environ.get("BENCH_LATENCY", "1") == "1":
+        # --full: second half of the BASELINE metric, outside the timed region, on
         # rank 0 after the process group is gone: a job of n replicas
         # (Master=1, Worker=n-1) submitted through the whole operator stack.
         # The trainer's buffers are released first (the job runs on these
@@ -331,6 +349,69 @@ def _param_tensors(trainer) -> list:
         return [p]
     m = getattr(trainer, "model", None)
     return [t for t in m.parameters()] if m is not None else []
+
+
+DUMP_BUDGET_BYTES = 60 * 2**20  # --dump-outputs writes at most 64 MB; the rest is .npy headers and slack
+
+
+def _step_outputs(trainer) -> dict:
+    """What a caller of the timed path holds after its last step, by name:
+    lists of tensors, each list read as one flat array."""
+    if hasattr(trainer, "loss_rows"):  # fused MNIST trainer: flat buffers
+        return {"params": [trainer.params], "momentum": [trainer.mom], "loss": [trainer.loss_rows]}
+    out = {"params": _param_tensors(trainer)}
+    opt = getattr(trainer, "opt", None)
+    state = getattr(opt, "state", None)
+    if state:
+        mom = [state[p]["momentum_buffer"] for p in out["params"]
+               if state.get(p, {}).get("momentum_buffer") is not None]
+        if mom:
+            out["momentum"] = mom
+    loss = getattr(trainer, "_loss", None)
+    if isinstance(loss, torch.Tensor):
+        out["loss"] = [loss]
+    else:
+        loss = trainer.last_loss()
+        if loss is not None:
+            out["loss"] = [torch.tensor([float(loss)])]
+    return out
+
+
+def _flat_f32(tensors, cap_elems: int, seed: int):
+    """The tensors as one flat float32 array on the host; more than
+    ``cap_elems`` elements: the same seeded sample of them on every run."""
+    import numpy as np
+
+    sizes = [t.numel() for t in tensors]
+    total = sum(sizes)
+    if total <= cap_elems:
+        parts = [t.detach().reshape(-1).to(torch.float32).cpu() for t in tensors]
+        return (torch.cat(parts) if parts else torch.zeros(0)).numpy()
+    g = torch.Generator().manual_seed(seed)
+    idx = torch.sort(torch.randint(total, (cap_elems,), generator=g)).values
+    bounds = torch.tensor([0] + sizes).cumsum(0)
+    cuts = torch.searchsorted(idx, bounds).tolist()
+    parts = []
+    for t, lo, a, b in zip(tensors, bounds.tolist(), cuts, cuts[1:]):
+        if b > a:
+            parts.append(t.detach().reshape(-1)[(idx[a:b] - lo).to(t.device)].to(torch.float32).cpu())
+    return np.ascontiguousarray(torch.cat(parts).numpy())
+
+
+def dump_outputs(directory: str, trainer) -> dict:
+    """``--dump-outputs``: DIR/<name>.npy for every array of
+    :func:`_step_outputs`; returns name -> element count written."""
+    import numpy as np
+
+    named = _step_outputs(trainer)
+    os.makedirs(directory, exist_ok=True)
+    cap = DUMP_BUDGET_BYTES // 4 // max(1, len(named))
+    written = {}
+    for name, tensors in sorted(named.items()):
+        arr = _flat_f32(tensors, cap, seed=1234)  # one seed: momentum is sampled where the parameters are
+        np.save(os.path.join(directory, name + ".npy"), arr)
+        written[name] = int(arr.size)
+    return written
 
 
 def measure_submit_to_first_step(gpu: bool, replicas: int = 1, timeout: float = 240.0) -> dict:
@@ -439,6 +520,9 @@ def run_model_bench(args, env, device, pdist, rccl_log=None):
     torch.cuda.synchronize(device)
     elapsed = pdist.all_reduce_max(time.perf_counter() - t0, device)
     identical = pdist.ranks_bit_identical(_param_tensors(trainer), device)
+    if args.dump_outputs and env.rank == 0:
+        print(f"[bench] outputs of the last step -> {args.dump_outputs}: {dump_outputs(args.dump_outputs, trainer)}",
+              file=sys.stderr)
     breakdown = None
     if args.breakdown:  # separate, untimed pass so event records do not perturb the measurement
         trainer.timer.enabled = True

@@ -129,7 +129,9 @@ def _port_free(port: int) -> bool:
         s.close()
 
 
-_PORT_LOCK_DIR = os.path.join("/tmp", "pto-port-locks")
+# one directory per user: lock files another user created cannot be opened
+# for writing, and a job would wait for its port for ever
+_PORT_LOCK_DIR = os.path.join("/tmp", f"pto-port-locks-{os.getuid()}")
 
 
 def _reserve_port(port: int):
@@ -206,7 +208,7 @@ class Kubelet:
         self.agent = agent or AgentClient(gpus=gpus, hbm_per_gpu=hbm_per_gpu,
                                           zygote=os.environ.get("PTO_ZYGOTE", "1") == "1")
         self.node_name = node_name
-        self.log_dir = log_dir or os.path.join(os.environ.get("TMPDIR", "/tmp"), "pto-pods")
+        self.log_dir = log_dir or os.path.join(os.environ.get("TMPDIR", "/tmp"), f"pto-pods-{os.getuid()}")
         os.makedirs(self.log_dir, exist_ok=True)
         self.images = dict(DEFAULT_IMAGES, **(images or {}))
         self.poll = poll_interval

@@ -20,7 +20,7 @@ def test_bench_two_ranks_cpu_json_line(sampler):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
            "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "6",
-           "--warmup", "2", "--cpu", "--dataset-size", "1280"] + (["--sampler"] if sampler else [])
+           "--warmup", "2", "--cpu", "--dataset-size", "1280", "--full"] + (["--sampler"] if sampler else [])
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=240, env=env, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [line for line in out.stdout.splitlines() if line.startswith("{")]
@@ -41,13 +41,13 @@ def test_bench_two_ranks_cpu_json_line(sampler):
 
 
 def test_bench_single_rank_reports_submit_to_first_step():
-    """World size 1: after the timed run, bench.py submits a 1-replica job
-    through the operator stack (fresh child agent + zygote) and reports
-    submit -> first optimizer step in the same JSON line."""
+    """World size 1, ``--full``: after the timed run, bench.py submits a
+    1-replica job through the operator stack (fresh child agent + zygote)
+    and reports submit -> first optimizer step in the same JSON line."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     env["OMP_NUM_THREADS"] = "2"
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "1", "--cpu",
-           "--dataset-size", "1280"]
+           "--dataset-size", "1280", "--full"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=300, env=env, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [line for line in out.stdout.splitlines() if line.startswith("{")]
@@ -57,6 +57,75 @@ def test_bench_single_rank_reports_submit_to_first_step():
     assert "error" not in lat, lat
     assert lat["job_state"] == "Succeeded" and lat["zygote_warm"] is True
     assert 0 < d["submit_to_first_step_s"] < 60
+
+
+def test_bench_plain_run_is_lean_and_dumps_outputs(tmp_path):
+    """Without ``--full`` the run stops at the result line (no job through
+    the operator stack); ``--dump-outputs DIR`` writes the last step's
+    arrays as float32 ``.npy`` files, the same from run to run."""
+    import numpy as np
+
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    env["OMP_NUM_THREADS"] = "2"
+    runs = []
+    for d in ("a", "b"):
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+               "--cpu", "--dataset-size", "640", "--dump-outputs", str(tmp_path / d)]
+        out = subprocess.run(cmd, capture_output=True, text=True, timeout=240, env=env, cwd=ROOT)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = [line for line in out.stdout.splitlines() if line.startswith("{")]
+        assert len(lines) == 1, out.stdout
+        res = json.loads(lines[0])
+        assert res["steps"] == 3 and res["ms_per_step"] > 0
+        assert "submit_to_first_step_s" not in res and "submit_to_first_step" not in res["config"]
+        runs.append({p.name: np.load(p) for p in sorted((tmp_path / d).iterdir())})
+    a, b = runs
+    assert set(a) == {"params.npy", "momentum.npy", "loss.npy"} == set(b)
+    assert a["params.npy"].shape == (431080,) == a["momentum.npy"].shape
+    for name in a:
+        assert a[name].dtype == np.float32 and np.isfinite(a[name]).all()
+        np.testing.assert_array_equal(a[name], b[name])
+    assert sum(v.nbytes for v in a.values()) <= 64 * 2**20
+
+
+def test_bench_dump_samples_large_outputs():
+    """More elements than the cap: a fixed seeded sample, in order, the same
+    on every call."""
+    import torch
+
+    sys.path.insert(0, ROOT)
+    import bench
+
+    ts = [torch.arange(0, 1000, dtype=torch.float64), torch.arange(1000, 1500, dtype=torch.float32)]
+    whole = bench._flat_f32(ts, 1500, seed=3)
+    assert whole.shape == (1500,) and whole[1234] == 1234
+    s1, s2 = bench._flat_f32(ts, 100, seed=3), bench._flat_f32(ts, 100, seed=3)
+    assert s1.shape == (100,) and (s1 == s2).all() and (s1[1:] >= s1[:-1]).all()
+    assert s1.min() >= 0 and s1.max() < 1500 and (s1 >= 1000).any() and (s1 < 1000).any()
+
+
+@pytest.mark.gpu
+def test_bench_dumps_fused_trainer_outputs(tmp_path):
+    """The fused trainer's flat buffers through ``--dump-outputs``'s writer:
+    parameters (the owed conv1 update committed), momentum and the last
+    step's per-sample loss, equal to the device buffers."""
+    import numpy as np
+    import torch
+
+    sys.path.insert(0, ROOT)
+    import bench
+    from pytorch_operator_1_amd.train.runner import build_trainer
+
+    tr = build_trainer("fused", device=torch.device("cuda", 0), batch_size=64, dataset_size=640, seed=1, rank=0)
+    tr.run(3)
+    torch.cuda.synchronize()
+    written = bench.dump_outputs(str(tmp_path), tr)
+    n = tr.params.numel()  # the flat buffer: 431,080 parameters at aligned offsets
+    assert n >= 431080 and written == {"params": n, "momentum": n, "loss": 64}
+    for name, t in (("params", tr.params), ("momentum", tr.mom), ("loss", tr.loss_rows)):
+        a = np.load(tmp_path / f"{name}.npy")
+        assert a.dtype == np.float32 and np.isfinite(a).all()
+        np.testing.assert_array_equal(a, t.detach().float().cpu().numpy().reshape(-1))
 
 
 def test_pto_bench_scaling_sweep_cpu():

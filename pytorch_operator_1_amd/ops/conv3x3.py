@@ -5,10 +5,16 @@ Forward: ``k_conv3x3_fwd`` -- and, when the consumer is a fused BatchNorm
 (``ops/bn.py``), the per-channel sums / sums of squares of the rounded
 outputs come out of the conv epilogue (:class:`ConvStats`), so the BN
 forward skips its statistics pass (a full read of the conv output).
-Backward: the input gradient of a stride-1 conv is the SAME kernel run on dY
-with the filter flipped and transposed (``k_conv3x3_wflip``); the stride-2
-input gradient and every weight gradient stay MIOpen's
-(``aten.convolution_backward``).  CPU / unsupported shapes: the stock conv.
+Backward (:func:`conv3x3_backward_plan`): the input gradient of a stride-1
+conv is the SAME kernel run on dY with the filter flipped and transposed
+(``k_conv3x3_wflip``) where that swapped launch meets the forward tile
+rules; the weight gradient is the package's split-reduction MFMA kernel
+(``csrc/kernels/conv3x3_wgrad.hip``, :func:`conv3x3_wgrad`: fp32, any C and
+K that are multiples of 64, bitwise repeatable) for the shapes
+``PTO_CONV3X3_WGRAD`` selects.  What is left -- the stride-2 input gradient,
+a C != K input gradient the tiles do not take, weight gradients not selected
+-- is MIOpen's (``aten.convolution_backward``).  CPU / unsupported shapes:
+the stock conv.
 
 Reference parity: the reference's workload is the MNIST ``Net``
 (``examples/mnist/mnist.py:17-33``); ResNet-50 is BASELINE.json config 3,
@@ -57,11 +63,39 @@ def conv3x3_supported(x: torch.Tensor, conv: nn.Conv2d) -> bool:
             and conv.padding == (1, 1) and conv.dilation == (1, 1) and conv.groups == 1 and conv.bias is None
             and conv.stride in ((1, 1), (2, 2)) and os.environ.get("PTO_CONV3X3", "1") == "1"):
         return False
-    C, K = conv.in_channels, conv.out_channels
-    if C % 64 or K % 64 or (K > 64 and K % 128) or (K > 256 and K % 256):
+    if conv.in_channels % 64 or not _fwd_tiles_ok(conv.out_channels):
         return False
     w = conv.weight
     return w.dtype == torch.float32 and w.is_contiguous(memory_format=_CL)
+
+
+def _fwd_tiles_ok(K: int) -> bool:
+    """The forward kernel's tile rules on its output channels: 64, or a
+    multiple of 128 up to 256, or a multiple of 256 above."""
+    return K >= 64 and not (K % 64 or (K > 64 and K % 128) or (K > 256 and K % 256))
+
+
+# (C, K, stride) whose weight gradient goes to the kernel under
+# PTO_CONV3X3_WGRAD=auto: the shapes where it was not slower than MIOpen's in
+# two separate runs at batch 256 (profiles/conv3x3_wgrad.md).
+WGRAD_AUTO = frozenset({(128, 128, 1), (256, 256, 2), (256, 256, 1), (512, 512, 1)})
+
+
+def conv3x3_backward_plan(C: int, K: int, stride: int) -> dict:
+    """Who computes each gradient of a supported conv: ``"kernel"`` or
+    ``"library"`` (MIOpen).  dx: the forward kernel on dY with C and K
+    swapped, so stride 1 only and C must meet the forward's rules on output
+    channels (and K, now the reduction, be a multiple of 64).  dw: the
+    ``PTO_CONV3X3_WGRAD`` switch, read at call time -- ``1`` the kernel for
+    every shape it takes, ``0`` the library, ``auto`` (default) the kernel
+    for the entries of :data:`WGRAD_AUTO`."""
+    dx = "kernel" if stride == 1 and K % 64 == 0 and _fwd_tiles_ok(C) else "library"
+    mode = os.environ.get("PTO_CONV3X3_WGRAD", "auto")
+    if mode not in ("auto", "0", "1"):
+        raise ValueError(f"PTO_CONV3X3_WGRAD must be auto, 0 or 1, not {mode!r}")
+    takes = C >= 64 and K >= 64 and C % 64 == 0 and K % 64 == 0 and stride in (1, 2)
+    dw = "kernel" if takes and (mode == "1" or (mode == "auto" and (C, K, stride) in WGRAD_AUTO)) else "library"
+    return {"dx": dx, "dw": dw}
 
 
 def _out_hw(h: int, s: int) -> int:
@@ -81,6 +115,34 @@ def _fwd(L, x, wb, stride, part=None):
 def stats_tiles(N: int, OH: int, OW: int, K: int) -> int:
     tm = _lib.lib().pto_conv3x3_tile_m(K)
     return (N * OH * OW + tm - 1) // tm
+
+
+def conv3x3_wgrad(x: torch.Tensor, dy: torch.Tensor, stride: int, workspace: torch.Tensor | None = None):
+    """Weight gradient of a 3x3 / pad-1 conv: ``x`` [N,C,H,W] and ``dy``
+    [N,K,OH,OW], bf16 channels-last, to fp32 (K,C,3,3) channels-last, sums
+    in fp32 and nothing rounded to bf16.  ``workspace``: fp32 scratch of at
+    least ``splits * K * 9 * C`` elements (any content; allocated if not
+    given).  Raises on a shape the kernel does not take."""
+    N, C, H, W = x.shape
+    K = dy.shape[1]
+    if not (x.is_cuda and x.dtype == dy.dtype == torch.bfloat16 and x.is_contiguous(memory_format=_CL)
+            and dy.is_contiguous(memory_format=_CL) and dy.device == x.device
+            and dy.shape == (N, K, _out_hw(H, stride), _out_hw(W, stride))):
+        raise ValueError("conv3x3_wgrad: x, dy must be bf16 channels-last CUDA tensors of matching conv shapes")
+    L = _lib.lib()
+    splits = L.pto_conv3x3_wgrad_splits(N, H, W, C, K, stride)
+    if splits < 1:
+        raise RuntimeError(f"conv3x3_wgrad: unsupported shape N={N} H={H} W={W} C={C} K={K} stride={stride}")
+    need = splits * K * 9 * C
+    if workspace is None:
+        workspace = torch.empty(need, device=x.device, dtype=torch.float32)
+    elif not (workspace.dtype == torch.float32 and workspace.device == x.device and workspace.is_contiguous()
+              and workspace.numel() >= need):
+        raise ValueError(f"conv3x3_wgrad: workspace must be contiguous fp32 with at least {need} elements")
+    dw = torch.empty(K, C, 3, 3, device=x.device, dtype=torch.float32, memory_format=_CL)
+    _lib.check(L.pto_conv3x3_wgrad(x.data_ptr(), dy.data_ptr(), dw.data_ptr(), workspace.data_ptr(), N, H, W, C, K,
+                                   stride, _lib.stream_ptr(x.device)), "conv3x3_wgrad")
+    return dw
 
 
 class _Conv3x3(torch.autograd.Function):
@@ -110,23 +172,28 @@ class _Conv3x3(torch.autograd.Function):
         x, wb = ctx.saved_tensors
         s = ctx.stride
         dy = dy.to(torch.bfloat16).contiguous(memory_format=_CL)
-        dx = None
-        if ctx.needs_input_grad[0] and s == 1:
+        K, C = wb.shape[0], wb.shape[1]
+        plan = conv3x3_backward_plan(C, K, s)
+        dx = dw = None
+        if ctx.needs_input_grad[0] and plan["dx"] == "kernel":
             L = _lib.lib()
-            K, C = wb.shape[0], wb.shape[1]
             wf = torch.empty(C, K, 3, 3, device=x.device, dtype=torch.bfloat16, memory_format=_CL)
             _lib.check(L.pto_conv3x3_wflip(None, wb.data_ptr(), wf.data_ptr(), K, C, _lib.stream_ptr(x.device)),
                        "conv3x3_wflip")
             dx = _fwd(L, dy, wf, 1)
+        if ctx.needs_input_grad[1] and plan["dw"] == "kernel":
+            dw = conv3x3_wgrad(x, dy, s)  # fp32, the master filter's layout
         need_dx_lib = ctx.needs_input_grad[0] and dx is None
-        dxl, dw, _ = torch.ops.aten.convolution_backward(dy, x, wb, None, [s, s], [1, 1], [1, 1], False, [0, 0], 1,
-                                                         [need_dx_lib, bool(ctx.needs_input_grad[1]), False])
-        if need_dx_lib:
-            dx = dxl
-        if dw is not None:
-            dw = dw.to(ctx.wdtype)
-            if dw.stride() != ctx.wstride:
-                dw = torch.empty_strided(ctx.wshape, ctx.wstride, dtype=dw.dtype, device=dw.device).copy_(dw)
+        need_dw_lib = ctx.needs_input_grad[1] and dw is None
+        if need_dx_lib or need_dw_lib:
+            dxl, dwl, _ = torch.ops.aten.convolution_backward(dy, x, wb, None, [s, s], [1, 1], [1, 1], False, [0, 0], 1,
+                                                              [need_dx_lib, need_dw_lib, False])
+            if need_dx_lib:
+                dx = dxl
+            if need_dw_lib:
+                dw = dwl.to(ctx.wdtype)
+        if dw is not None and dw.stride() != ctx.wstride:
+            dw = torch.empty_strided(ctx.wshape, ctx.wstride, dtype=dw.dtype, device=dw.device).copy_(dw)
         return dx, dw, None, None, None
 
 

@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
 """ResNet-50's 3x3 convs at batch 256: the MFMA implicit-GEMM kernel
 (ops/conv3x3.py) against MIOpen (F.conv2d / aten.convolution_backward,
-cudnn.benchmark on), forward and stride-1 data gradient, median of HIP-event
-timed repeats.  One JSON line per shape.
+cudnn.benchmark on), forward, stride-1 data gradient and weight gradient
+(ops.conv3x3.conv3x3_wgrad: kernel + reduce, against MIOpen's weight gradient
+alone), median of HIP-event timed repeats.  One JSON line per shape.
 
     python tools/conv3x3_bench.py [--batch 256] [--reps 20]
 """
@@ -48,13 +49,14 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--shapes", default="", help="only these C:H:stride shapes, comma-separated")
     ap.add_argument("--no-dgrad", action="store_true")
+    ap.add_argument("--no-wgrad", action="store_true")
     ap.add_argument("--variants", default="64:2", help="kernel variants bk:pf to time, comma-separated "
                                                        "(bk = K-step channels 32|64, pf = prefetch steps 1|2)")
     a = ap.parse_args()
     torch.backends.cudnn.benchmark = True
     dev = torch.device("cuda", 0)
     L = _lib.lib()
-    tot = {"ours_fwd": 0.0, "lib_fwd": 0.0, "ours_dgrad": 0.0, "lib_dgrad": 0.0}
+    tot = {"ours_fwd": 0.0, "lib_fwd": 0.0, "ours_dgrad": 0.0, "lib_dgrad": 0.0, "ours_wgrad": 0.0, "lib_wgrad": 0.0}
     want = {tuple(int(u) for u in v.split(":")) for v in a.shapes.split(",") if v}
     for C, H, s in SHAPES:
         if want and (C, H, s) not in want:
@@ -85,8 +87,24 @@ def main():
         ours = best
         tot["ours_fwd"] += ours
         tot["lib_fwd"] += lib
+        dy = torch.randn(N, C, OH, OH, device=dev).to(torch.bfloat16).contiguous(memory_format=torch.channels_last)
+        if not a.no_wgrad:
+            splits = L.pto_conv3x3_wgrad_splits(N, H, H, C, C, s)
+            ws = torch.empty(splits * C * 9 * C, device=dev)
+
+            def lib_wgrad():
+                return torch.ops.aten.convolution_backward(dy, x, wb, None, [s, s], [1, 1], [1, 1], False, [0, 0],
+                                                           1, [False, True, False])
+
+            wref = lib_wgrad()[1].float()
+            wours = c3.conv3x3_wgrad(x, dy, s, ws)
+            ow, lw = timed(lambda: c3.conv3x3_wgrad(x, dy, s, ws), a.reps), timed(lib_wgrad, a.reps)
+            row.update(wgrad_us=round(ow, 1), miopen_wgrad_us=round(lw, 1), wgrad_splits=splits,
+                       wgrad_tflops=round(flops / ow / 1e6, 1),
+                       wgrad_vs_miopen_relerr=float((wours - wref).abs().max() / wref.abs().max()))
+            tot["ours_wgrad"] += ow
+            tot["lib_wgrad"] += lw
         if s == 1 and not a.no_dgrad:
-            dy = torch.randn(N, C, OH, OH, device=dev).to(torch.bfloat16).contiguous(memory_format=torch.channels_last)
             wf = torch.empty_like(wb)
 
             def ours_dgrad():

@@ -8,6 +8,9 @@ large-model DDP config, built MI355X-first:
 * bf16 parameters / activations; GEMMs on hipBLASLt through ``F.linear``
   with the projections fused to cut launches and re-reads: one QKV GEMM
   (``wqkv = [wq; wk; wv]``), one gate|up GEMM (``w13 = [w1; w3]``).
+  ``PTO_GEMM=1`` (``auto``: per measured shape, none so far) puts them on
+  the package's own MFMA GEMM instead (:mod:`..ops.gemm`), which needs
+  neither the ``W^T`` copies nor the activation transposes.
 * Everything between GEMMs is one HIP kernel per boundary
   (:mod:`..ops.llm`): residual-add + RMSNorm (its backward also adds the
   residual-stream gradient), RoPE in place on the QKV output, SwiGLU, and
@@ -127,8 +130,9 @@ class LlamaBlock(nn.Module):
         h, y = llm.add_rmsnorm(h, attn, self.ffn_norm, c.norm_eps)
         # the SwiGLU backward hands w13's weight gradient its output
         # gradient already transposed (ops/llm.py TStash)
+        # (a weight gradient on the package's GEMM reads dY as stored: no stash)
         st = llm.TStash() if getattr(self.w13, "dw_kcontig", False) and os.environ.get("PTO_SWIGLU_T", "1") == "1" \
-            else None
+            and _plan("wgrad", y, self.w13) == "lib" else None
         mlp = _lin(llm.swiglu(_lin(y, self.w13, st), st), self.w2)
         return h, mlp
 
@@ -155,12 +159,21 @@ class LlamaBlock(nn.Module):
 def _lin(x, mod: nn.Linear, tstash=None):
     """Bias-free linear; with a transposed weight copy attached
     (:meth:`Llama.enable_transposed_dgrad`) the input gradient uses it."""
-    wt = getattr(mod, "weight_t", None)
-    if wt is None:
-        return F.linear(x, mod.weight)
-    from ..ops import llm
+    from ..ops import gemm
 
-    return llm.linear_tw(x, mod.weight, wt, getattr(mod, "dw_kcontig", False), tstash)
+    # each GEMM on the package's kernel or on the library (PTO_GEMM); all on
+    # the library, it is F.linear / llm.linear_tw itself
+    return gemm.linear(x, mod.weight, getattr(mod, "weight_t", None), getattr(mod, "dw_kcontig", False), tstash)
+
+
+def _plan(kind: str, x, mod: nn.Linear) -> str:
+    """Who runs the GEMM ``kind`` of ``mod`` on ``x``: ``ops.gemm.gemm_plan``
+    for bf16 HIP tensors, the library for anything else."""
+    if not (x.is_cuda and x.dtype == torch.bfloat16 and mod.weight.dtype == torch.bfloat16):
+        return "lib"
+    from ..ops import gemm
+
+    return gemm.gemm_plan(kind, x.numel() // x.shape[-1], mod.out_features, mod.in_features)
 
 
 def _rmsnorm_ref(x, w, eps):

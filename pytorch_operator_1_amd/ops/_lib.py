@@ -30,7 +30,7 @@ HIPCC = os.environ.get("HIPCC", shutil.which("hipcc") or "/opt/rocm/bin/hipcc")
 
 HIP_SOURCES = ("kernels/mnist_kernels.hip", "kernels/common_kernels.hip", "kernels/optim_kernels.hip",
                "kernels/llm_kernels.hip", "kernels/attention.hip", "kernels/bn_kernels.hip", "kernels/conv3x3.hip",
-               "kernels/conv3x3_wgrad.hip", "comm/xgmi_allreduce.hip")
+               "kernels/conv3x3_wgrad.hip", "kernels/gemm_bf16.hip", "comm/xgmi_allreduce.hip")
 
 _lock = threading.Lock()
 # launchers return an int hipError; these few return something else
@@ -156,6 +156,9 @@ _SIGS = {
     # 3x3 weight gradient (csrc/kernels/conv3x3_wgrad.hip)
     "pto_conv3x3_wgrad_splits": [_I, _I, _I, _I, _I, _I],
     "pto_conv3x3_wgrad": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
+    # bf16 MFMA GEMM, NT / NN / TN (csrc/kernels/gemm_bf16.hip)
+    "pto_gemm_bf16": [_I, _P, _L, _P, _L, _P, _L, _I, _L, _L, _L, _P],
+    "pto_gemm_bf16_supported": [_I, _L, _L, _L, _L, _L, _L],
     "pto_maxpool_fwd": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P],
     "pto_stem_fwd": [_P, _P, _L, _L, _L, _L, _P, _P, _I, _P],
     "pto_maxpool_bwd": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P],

@@ -218,7 +218,8 @@ class LlamaTrainer(CheckpointMixin):
         self.batch_size, self.seq_len = batch_size, seq_len
         self.model = Llama(self.cfg, impl=impl, device=device, checkpoint=checkpoint)
         self.model.train()
-        # W^T copies for K-contiguous dgrad GEMMs (PTO_WT=0: plain F.linear backward)
+        # W^T copies for K-contiguous dgrad GEMMs (PTO_WT=0: plain F.linear backward;
+        # with PTO_GEMM=1 the package's NN GEMM then reads W as stored, ops/gemm.py)
         self.transposed_dgrad = impl == "hip" and os.environ.get("PTO_WT", "1") == "1"
         if self.transposed_dgrad:
             self.model.enable_transposed_dgrad()

@@ -1758,6 +1758,59 @@ PTO_DEV void dw1_sgd_tile(int tile, const float* __restrict__ dh1, const float* 
   }
 }
 
+// 16-byte store of fc1.weight / its momentum that writes through the L2
+// (sc1).  k_bwd_all's D role leaves 3.2 MB of freshly written parameters
+// and momentum behind; left dirty in the L2s they are written back at the
+// launch boundary, on the next launch's time (plain stores: step 33.67 us,
+// write-through: 33.26 us, profiles/bwd_placement.md).  A buffer store:
+// `i` (floats) past the matrix is dropped by the hardware's range check.
+PTO_DEV void st4_wt(float* base, int i, float4 v) {
+  constexpr int AUX_SC1 = 16;
+  __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(pto_ar::v4u, v),
+                                         pto_ar::mkbuf(base, (long long)F1OUT * F1IN * 4).r, i * 4, 0, AUX_SC1);
+}
+
+// The same tile computed TRANSPOSED (the two MFMA operands swapped: a2p is
+// the A operand, dh1 the B operand), so a lane's four accumulator registers
+// are four consecutive fc1.weight columns nt*16 + 4*(lane >> 4) + rr of ONE
+// row mt*16 + (lane & 15): p and m each move as one 16-byte load and one
+// 16-byte store per lane (dw1_sgd_tile: four dword accesses each, a 64-byte
+// segment per 16 lanes).  Every element's products and their k order are
+// dw1_sgd_tile's, so the result is bitwise the same
+// (tests/test_bwd_placement_gpu.py compares the two).  SGD on fc1.weight,
+// or, grads-only (gout != nullptr), the gradient stored.  pw / mw / gout
+// 16-byte aligned (the launcher checks).
+PTO_DEV void dw1_tile_t(int tile, const float* __restrict__ dh1, const float* __restrict__ a2p,
+                        float* __restrict__ pw, float* __restrict__ mw, float* __restrict__ gout, int B,
+                        const SgdArgs& a) {
+  constexpr int MT = (F1OUT + 15) / 16, NT = (F1IN + 15) / 16;
+  static_assert(F1IN % 16 == 0, "a lane's four columns never cross the row end");
+  if (tile >= MT * NT) return;
+  const int mt = tile % MT, nt = tile / MT, lane = threadIdx.x & 63;
+  const int row = mt * 16 + (lane & 15);
+  const bool ok = row < F1OUT;
+  const int i = (ok ? row : 0) * F1IN + nt * 16 + (lane >> 4) * 4;
+  float4 pv = {0.f, 0.f, 0.f, 0.f}, mv = pv;
+  if (!gout) {  // before the MMA chain: in flight with the operand loads
+    pv = *reinterpret_cast<const float4*>(pw + i);
+    mv = *reinterpret_cast<const float4*>(mw + i);
+  }
+  const float lr = gout ? 0.f : *a.lr;
+  const f32x4 acc =
+      wave_tile_16x16<LAY_KROW, LAY_KROW, 4>(a2p, F1IN, dh1, F1OUT, F1IN, F1OUT, B, nt * 16, mt * 16, 0, B);
+  if (!ok) return;
+  if (gout) {
+    *reinterpret_cast<float4*>(gout + i) = float4{acc[0], acc[1], acc[2], acc[3]};
+    return;
+  }
+  sgd_elem(pv.x, acc[0], mv.x, lr, a.mom, a.wd, a.gscale, a.nesterov);
+  sgd_elem(pv.y, acc[1], mv.y, lr, a.mom, a.wd, a.gscale, a.nesterov);
+  sgd_elem(pv.z, acc[2], mv.z, lr, a.mom, a.wd, a.gscale, a.nesterov);
+  sgd_elem(pv.w, acc[3], mv.w, lr, a.mom, a.wd, a.gscale, a.nesterov);
+  st4_wt(pw, i, pv);
+  st4_wt(mw, i, mv);
+}
+
 // One wave: the two dW1 tiles (mt, 2j) and (mt, 2j+1) side by side -- they
 // share the dh1 operand (16 loads per lane instead of 32 for two tiles) and
 // their four MFMA chains interleave, so a wave holds two tiles for about
@@ -1919,6 +1972,8 @@ __global__ __launch_bounds__(256) void k_conv1_bwd(const float* __restrict__ g1,
 //   D  dW1 = dh1^T a2p tiles consumed by SGD on fc1.weight.
 //   F  dW2 (fc2) tiles, db1, db2 with SGD epilogues.
 // Block 0 advances the batch cursor and marks conv1's update as owed.
+// A, B and D decode their work from an XCD-affine logical id (bwd_xcd_id),
+// so the blocks that share inputs share an L2.
 // dW1 tiles (16 x 16 of fc1.weight's gradient) per wave of a k_bwd_all D
 // block.  A grid of 256-thread blocks starts at ~3.6 ns per block
 // (tools/dispatch_ramp_probe.py: 1422 blocks take 4.6-5.4 us just to all be
@@ -1956,6 +2011,43 @@ __host__ __device__ constexpr int bwd_order(int i) {
   constexpr int o[6][5] = {{0, 1, 2, 3, 4}, {3, 2, 4, 0, 1}, {3, 2, 0, 1, 4}, {2, 3, 0, 1, 4},
                            {3, 4, 2, 0, 1}, {0, 1, 3, 2, 4}};
   return o[PTO_BWD_ORDER][i];
+}
+// XCD-affine logical block id.  The hardware hands workgroup i to XCD i % 8
+// (observed, not promised: a wrong guess only costs speed), and the eight
+// per-XCD L2s are cold at every launch, so a role whose blocks share inputs
+// by LOGICAL neighbourhood (a wgrad chunk, a sample, an a2p column tile)
+// wants each XCD to hold one contiguous run of logical ids.  For the role
+// block `bid` (0 <= bid < T) of a role whose first block has global id `o`:
+// slot x = (o + bid) & 7; the role's blocks of slot s are bid = d_s + 8 j
+// with d_s = (s - o) & 7, so the rank inside the slot is bid >> 3 and the
+// logical id is (blocks of slots 0..x-1) + rank.  A bijection of 0..T-1 for
+// every T and o (slot sizes differ by at most one).
+__host__ __device__ inline int bwd_xcd_id(int bid, int o, int T) {
+  const int x = (o + bid) & 7;
+  int base = 0;
+  for (int s = 0; s < x; ++s) {
+    const int d = (s - o) & 7;
+    base += d < T ? ((T - 1 - d) >> 3) + 1 : 0;
+  }
+  return base + (bid >> 3);
+}
+// Role of global block `gid` of a k_bwd_all grid with cnt[role] blocks per
+// role (role ids C 0, F 1, A 2, B 3, D 4; ranges in bwd_order()), and in
+// *id its id inside the role: XCD-affine for A, B and D, the plain rank for
+// the short C and F ranges.  -1 past the grid.
+__host__ __device__ inline int bwd_role_id(int gid, const int cnt[5], int* id) {
+  int o = 0;
+#pragma unroll
+  for (int i = 0; i < 5; ++i) {
+    const int r = bwd_order(i);
+    if (gid - o < cnt[r]) {
+      *id = r >= 2 ? bwd_xcd_id(gid - o, o, cnt[r]) : gid - o;
+      return r;
+    }
+    o += cnt[r];
+  }
+  *id = gid - o;
+  return -1;
 }
 constexpr int bwd_n_dw1_blocks(bool pair) {
   return pair ? ((((F1OUT + 15) / 16) * ((F1IN + 15) / 16) / 2) + 3) / 4
@@ -2036,20 +2128,12 @@ __global__ __launch_bounds__(256) void k_bwd_all(BwdAllArgs A) {
   }
   // block order (role ranges of the grid): bwd_order(); a grid of
   // 1,422 blocks takes ~5 us just to start (tools/dispatch_ramp_probe.py),
-  // so the order decides which roles start late
-  int role = 4;
-  {
-    const int cnt[5] = {A.nC, A.nF, A.nA, A.nB, A.nD};  // role ids: C F A B D
-#pragma unroll
-    for (int i = 0; i < 5; ++i) {
-      const int r = bwd_order(i);
-      if (bid < cnt[r]) {
-        role = r;
-        break;
-      }
-      bid -= cnt[r];
-    }
-  }
+  // so the order decides which roles start late, and within A, B and D the
+  // XCD-affine logical id (bwd_xcd_id) decides which blocks share an L2.
+  // Everything below works on the logical id; the cursor and the hz
+  // re-zero above are indexed by the physical block.
+  const int cnt[5] = {A.nC, A.nF, A.nA, A.nB, A.nD};  // role ids: C F A B D
+  const int role = bwd_role_id(blockIdx.x, cnt, &bid);
   if (role == 0) {  // C
     const int oc = bid * 4 + wv;
     if (oc >= C2) return;
@@ -2157,23 +2241,34 @@ __global__ __launch_bounds__(256) void k_bwd_all(BwdAllArgs A) {
                    A.wpart != nullptr);
     return;
   }
-  if (role == 4) {  // D
+  if (role == 4) {  // D: tile = 4 * block + wave, a2p-column-major (nt = tile / MT), so an XCD's run of logical
+                    // blocks covers 6-7 of the 50 a2p column tiles
+    float* const gout = A.grads_only ? A.g1w : nullptr;
     if (A.dpair) {  // two dW1 tiles per wave, side by side
-      dw1_tile_pair(bid * 4 + wv, A.dh1, A.a2p, A.p1w, A.m1w, A.grads_only ? A.g1w : nullptr, A.B, A.a);
+      dw1_tile_pair(bid * 4 + wv, A.dh1, A.a2p, A.p1w, A.m1w, gout, A.B, A.a);
       return;
     }
     // BWD_DTPW dW1 tiles per wave, one after the other (no barriers in this role)
 #pragma unroll
-    for (int j = 0; j < BWD_DTPW; ++j) {
-      const int vb = bid * BWD_DTPW + j;
-      if (A.grads_only)
-        block_gemm_4tiles<LAY_KROW, LAY_KROW, EpiStore, 4>(A.dh1, F1OUT, A.a2p, F1IN, F1OUT, F1IN, A.B, vb,
-                                                          EpiStore{A.g1w, F1IN});
-      else
-        dw1_sgd_tile(vb * 4 + wv, A.dh1, A.a2p, A.p1w, A.m1w, A.B, A.a);
-    }
+    for (int j = 0; j < BWD_DTPW; ++j)
+      dw1_tile_t((bid * BWD_DTPW + j) * 4 + wv, A.dh1, A.a2p, A.p1w, A.m1w, gout, A.B, A.a);
     return;
   }
+}
+
+// Test-only (pto_dw1_tiles): k_bwd_all's D role on its own, plain block
+// order.  form 0: the untransposed routines the role used before
+// (dw1_sgd_tile, or block_gemm_4tiles' store when gout is given); form 1:
+// dw1_tile_t; form 2: dw1_tile_pair (half the grid).
+__global__ __launch_bounds__(256) void k_dw1_tiles(const float* __restrict__ dh1, const float* __restrict__ a2p,
+                                                   float* __restrict__ pw, float* __restrict__ mw,
+                                                   float* __restrict__ gout, int B, SgdArgs a, int form) {
+  const int bid = blockIdx.x, wv = threadIdx.x >> 6;
+  if (form == 2) dw1_tile_pair(bid * 4 + wv, dh1, a2p, pw, mw, gout, B, a);
+  else if (form == 1) dw1_tile_t(bid * 4 + wv, dh1, a2p, pw, mw, gout, B, a);
+  else if (gout)
+    block_gemm_4tiles<LAY_KROW, LAY_KROW, EpiStore, 4>(dh1, F1OUT, a2p, F1IN, F1OUT, F1IN, B, bid, EpiStore{gout, F1IN});
+  else dw1_sgd_tile(bid * 4 + wv, dh1, a2p, pw, mw, B, a);
 }
 
 // Host-side flush of an owed conv1 update (before the parameters are read
@@ -2557,6 +2652,8 @@ PTO_API int pto_bwd_all(const float* g2, const uint8_t* code2, const float* a1p,
   if (bidx && nbatches < 1) return -1;
   if (B < 1 || nrep < 1 || nrep > C1_MAXREP || (nrep > 1 && !c1rep)) return -1;
   if (wpart && nrep != B) return -1;  // deterministic mode: one conv1 replica per sample
+  if ((((uintptr_t)(p + off_fc1w)) | ((uintptr_t)(g + off_fc1w)) | ((uintptr_t)(m + off_fc1w))) & 15)
+    return -1;  // 16-byte accesses of fc1.weight's rows (dw1_tile_t)
   BwdAllArgs A;
   A.g2 = g2; A.code2 = code2; A.a1p = a1p; A.w2f = w2f; A.x = x; A.code1 = code1;
   A.gw1 = g + off_c1w; A.gb1 = g + off_c1b;
@@ -2590,5 +2687,33 @@ PTO_API int pto_bwd_all(const float* g2, const uint8_t* code2, const float* a1p,
   const size_t ldsB = B2_LDS_FLOATS * sizeof(float);
   const size_t lds = ldsA > ldsB ? ldsA : ldsB;
   hipLaunchKernelGGL(HIP_KERNEL_NAME(k_bwd_all<BWD_WCHUNK, BWD_WNTW>), dim3(A.nA + A.nB + A.nC + A.nD + A.nF), dim3(256), lds, s, A);
+  LAUNCH_CHECK();
+}
+
+// Test entry points (tests/test_bwd_placement_gpu.py).
+// Host only: role[i] / id[i] of every physical block i of pto_bwd_all's grid
+// at batch B (dpair: the tile-pair D grid) by the kernel's own
+// bwd_role_id; returns the grid size, or -1 if it exceeds cap.
+PTO_API int pto_bwd_block_map(int B, int dpair, int* role, int* id, int cap) {
+  if (B < 1) return -1;
+  const int cnt[5] = {(C2 + 3) / 4, (((NCLS + 15) / 16) * ((F1OUT + 15) / 16) + 3) / 4 + 9,
+                      ((B + BWD_WCHUNK - 1) / BWD_WCHUNK) * (32 / BWD_WNTW), B * B2_ICG,
+                      bwd_n_dw1_blocks(dpair != 0 && BWD_DTPW == 1)};
+  const int n = cnt[0] + cnt[1] + cnt[2] + cnt[3] + cnt[4];
+  if (n > cap) return -1;
+  for (int i = 0; i < n; ++i) role[i] = bwd_role_id(i, cnt, id + i);
+  return n;
+}
+
+// k_bwd_all's D role alone (k_dw1_tiles): form 0 untransposed, 1 transposed,
+// 2 tile pairs; gout != nullptr stores the gradient instead of applying SGD.
+PTO_API int pto_dw1_tiles(const float* dh1, const float* a2p, float* pw, float* mw, float* gout, int B,
+                          const float* lr, float mom, float wd, float gscale, int nesterov, int form,
+                          hipStream_t s) {
+  if (B < 1 || form < 0 || form > 2 || (!gout && (!pw || !mw || !lr))) return -1;
+  if ((((uintptr_t)pw) | ((uintptr_t)mw) | ((uintptr_t)gout)) & 15) return -1;
+  const int nblk = form == 2 ? bwd_n_dw1_blocks(true) : (((F1OUT + 15) / 16) * ((F1IN + 15) / 16) + 3) / 4;
+  hipLaunchKernelGGL(k_dw1_tiles, dim3(nblk), dim3(256), 0, s, dh1, a2p, pw, mw, gout, B,
+                     sgd_args(lr, mom, wd, gscale, nesterov), form);
   LAUNCH_CHECK();
 }

@@ -104,6 +104,9 @@ _SIGS = {
     "pto_synth_mnist": [_P, _P, _L, ctypes.c_ulonglong, _P],
     "pto_bwd_all": [_P] * 13 + [_L] * 8 + [_P, _P, _L, _P, _I, _P, _F, _F, _F, _I, _P, _I, _I, _I, _P, _P, _I,
                                           _P],
+    # test entry points: k_bwd_all's block map (host only) and its D role alone
+    "pto_bwd_block_map": [_I, _I, _P, _P, _I],
+    "pto_dw1_tiles": [_P, _P, _P, _P, _P, _I, _P, _F, _F, _F, _I, _I, _P],
     "pto_conv1_commit": [_P, _P, _P, _I, _P, _P, _F, _F, _F, _I, _P, _I, _I, _P],
     "pto_mnist_ddp_sgd": [_P, _P, _P, _I, _I, _I, _P, _I, _P, _F, _F, _F, _I, _P, _L, _P],
     "pto_fc2_ce_dx": [_P] * 9 + [_I, _F, _P, _P, _P, _P, _I, _P, _P, _F, _F, _F, _I, _P, _I, _I, _P, _P, _P, _L,

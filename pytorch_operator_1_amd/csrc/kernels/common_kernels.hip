@@ -18,11 +18,16 @@ namespace {
 
 constexpr int SGD_CHUNK = 256 * 4;  // elements per block (one float4 per thread: max parallelism)
 
+// CLIP: the gradient scale is multiplied by *gscale_ptr (the global-norm
+// clip coefficient, optim_kernels.hip).  A template parameter, so the plain
+// instance is the kernel it was, instruction for instruction.
+template <bool CLIP>
 __global__ __launch_bounds__(256) void k_sgd_multi(const SgdTensor* __restrict__ ts,
                                                    const int* __restrict__ block_start, int ntensors,
                                                    const float* __restrict__ lr_ptr, float lr, float mom, float wd,
                                                    float gscale, int nesterov, int zero_grad,
-                                                   long long* __restrict__ bidx, long long nbatches) {
+                                                   long long* __restrict__ bidx, long long nbatches,
+                                                   const float* __restrict__ gscale_ptr) {
   // The optimizer is the last launch of a training step: it also advances
   // the device-side batch cursor read by the next step's kernels.
   if (bidx && blockIdx.x == 0 && threadIdx.x == 0) *bidx = (*bidx + 1) % nbatches;
@@ -35,6 +40,7 @@ __global__ __launch_bounds__(256) void k_sgd_multi(const SgdTensor* __restrict__
   }
   const SgdTensor t = ts[lo];
   if (lr_ptr) lr = *lr_ptr;
+  if (CLIP) gscale *= *gscale_ptr;
   const long long base = (long long)(bid - block_start[lo]) * SGD_CHUNK;
   const bool vec = ((((uintptr_t)t.p) | ((uintptr_t)t.g) | ((uintptr_t)t.m)) & 15) == 0;
   {
@@ -299,8 +305,24 @@ PTO_API int pto_sgd_multi(const SgdTensor* ts, const int* block_start, int ntens
                           const float* lr_ptr, float lr, float mom, float wd, float gscale, int nesterov,
                           int zero_grad, long long* bidx, long long nbatches, hipStream_t s) {
   if (nblocks <= 0) return 0;
-  hipLaunchKernelGGL(k_sgd_multi, dim3(nblocks), dim3(256), 0, s, ts, block_start, ntensors, lr_ptr, lr, mom, wd,
-                     gscale, nesterov, zero_grad, bidx, nbatches);
+  hipLaunchKernelGGL(k_sgd_multi<false>, dim3(nblocks), dim3(256), 0, s, ts, block_start, ntensors, lr_ptr, lr, mom,
+                     wd, gscale, nesterov, zero_grad, bidx, nbatches, nullptr);
+  return (int)hipGetLastError();
+}
+
+// pto_sgd_multi with the gradient scale multiplied by *gscale_ptr (device
+// memory: the clip coefficient of pto_grad_norm_finalize), read at run time
+// so a captured launch picks up each replay's coefficient.
+PTO_API int pto_sgd_multi_clip(const SgdTensor* ts, const int* block_start, int ntensors, int nblocks,
+                               const float* lr_ptr, float lr, float mom, float wd, float gscale,
+                               const float* gscale_ptr, int nesterov, int zero_grad, long long* bidx,
+                               long long nbatches, hipStream_t s) {
+  if (nblocks <= 0) return 0;
+  if (!gscale_ptr)
+    return pto_sgd_multi(ts, block_start, ntensors, nblocks, lr_ptr, lr, mom, wd, gscale, nesterov, zero_grad, bidx,
+                         nbatches, s);
+  hipLaunchKernelGGL(k_sgd_multi<true>, dim3(nblocks), dim3(256), 0, s, ts, block_start, ntensors, lr_ptr, lr, mom,
+                     wd, gscale, nesterov, zero_grad, bidx, nbatches, gscale_ptr);
   return (int)hipGetLastError();
 }
 

@@ -12,6 +12,7 @@
 // 2 x 16-byte fp32 accesses per state tensor (Guideline 13).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "mfma_f32.h"
 
 struct AdamTensor {
   void* p;         // param: bf16 (mixed) or fp32
@@ -46,11 +47,24 @@ __device__ __forceinline__ void adam_elem(float& w, float g, float& m, float& v,
   w = w * (1.f - h.lr * h.wd) - h.lr * mhat / (sqrtf(vhat) + h.eps);  // decoupled decay (AdamW)
 }
 
-template <bool MIXED>
+// CLIP: each gradient is multiplied by *gscale_ptr (the global-norm clip
+// coefficient of k_grad_norm_finalize, read once per thread) on its way into
+// adam_elem, so the effective scale is gscale * coef.  Two things are
+// deliberate (profiles/grad_clip.md):
+//  * a template parameter, not a test of the pointer: with the test in the
+//    kernel hipcc contracted adam_elem's multiply-adds differently (another
+//    sequence of fp instructions, so other roundings, for callers that pass
+//    no pointer) and the launch was 0.6-1.0 % slower.  The plain instance
+//    keeps the instructions it had.
+//  * the coefficient goes onto the gradient, not into h.gscale: h.gscale
+//    stays the kernel argument it is in the plain instance, adam_elem
+//    compiles to the same operations in both, and a coefficient of exactly
+//    1.0 (max_norm = inf) gives bit for bit the unclipped update.
+template <bool MIXED, bool CLIP>
 __global__ __launch_bounds__(256) void k_adamw_multi(const AdamTensor* __restrict__ ts,
                                                      const int* __restrict__ block_start, int ntensors,
                                                      const float* __restrict__ lr_ptr, AdamHyper h,
-                                                     int zero_grad) {
+                                                     int zero_grad, const float* __restrict__ gscale_ptr) {
   int lo = 0, hi = ntensors - 1;
   const int bid = blockIdx.x;
   while (lo < hi) {
@@ -59,6 +73,7 @@ __global__ __launch_bounds__(256) void k_adamw_multi(const AdamTensor* __restric
   }
   const AdamTensor t = ts[lo];
   if (lr_ptr) h.lr = *lr_ptr;
+  const float coef = CLIP ? *gscale_ptr : 1.f;
   const long long i0 = (long long)(bid - block_start[lo]) * ADAM_CHUNK + (long long)threadIdx.x * 8;
   if (i0 >= t.n) return;
   const bool full = i0 + 8 <= t.n;
@@ -79,7 +94,7 @@ __global__ __launch_bounds__(256) void k_adamw_multi(const AdamTensor* __restric
       uint16_t out[8];
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
-        adam_elem(w[j], bf2f(gs[j]), m[j], v[j], h);
+        adam_elem(w[j], CLIP ? bf2f(gs[j]) * coef : bf2f(gs[j]), m[j], v[j], h);
         out[j] = f2bf(w[j]);
       }
       reinterpret_cast<float4*>(t.master + i0)[0] = float4{w[0], w[1], w[2], w[3]};
@@ -93,7 +108,7 @@ __global__ __launch_bounds__(256) void k_adamw_multi(const AdamTensor* __restric
     } else {
       for (long long e = i0; e < i0 + 8 && e < t.n; ++e) {
         float w = t.master[e], m = t.m[e], v = t.v[e];
-        adam_elem(w, bf2f(gb[e]), m, v, h);
+        adam_elem(w, CLIP ? bf2f(gb[e]) * coef : bf2f(gb[e]), m, v, h);
         t.master[e] = w; t.m[e] = m; t.v[e] = v;
         pb[e] = f2bf(w);
         if (zero_grad) gb[e] = 0;
@@ -104,10 +119,158 @@ __global__ __launch_bounds__(256) void k_adamw_multi(const AdamTensor* __restric
     float* g = reinterpret_cast<float*>(t.g);
     for (long long e = i0; e < i0 + 8 && e < t.n; ++e) {
       float w = p[e], m = t.m[e], v = t.v[e];
-      adam_elem(w, g[e], m, v, h);
+      adam_elem(w, CLIP ? g[e] * coef : g[e], m, v, h);
       p[e] = w; t.m[e] = m; t.v[e] = v;
       if (zero_grad) g[e] = 0.f;
     }
+  }
+}
+
+// ---- global gradient norm (clip_grad_norm_ without a host sync) ----------
+//
+// Stage 1, k_grad_sqnorm_multi: sum of squares over every gradient of a
+// launch table (AdamTensor or SgdTensor records: the gradient pointer is the
+// second field, the element count the last).  The gradients are cut into
+// chunks of SQN_CHUNK elements (8 per thread, k_adamw_multi's access
+// pattern); chunk_start[t] is the first chunk of tensor t and
+// chunk_start[ntensors] the total.  A workgroup owns SQN_CPB consecutive
+// chunks, whatever tensors they belong to, and writes ONE partial.
+//
+// Stage 2, k_grad_norm_finalize: one workgroup sums the partials and writes
+// {total_norm, coef}; the optimizer kernels multiply their gradient scale
+// by coef, read from device memory.
+//
+// Every replica of a DDP job must derive the same coefficient from the same
+// (all-reduced) gradients, so the order of every addition is fixed by the
+// table alone: no atomics, no dependence on which block finishes first.
+//   thread: 8 accumulators (element j of its 8), one fma per chunk in chunk
+//           order, then ((a0+a1)+(a2+a3))+((a4+a5)+(a6+a7));
+//   wave:   wave_sum (6 exchange steps);   block: waves 0..3 in order.
+constexpr int SQN_CHUNK = 256 * 8;  // elements per chunk
+constexpr int SQN_CPB = 32;         // chunks per workgroup (128 KB of bf16): 8 B params -> 122k partials, 0.5 MB
+constexpr int FIN_THREADS = 1024;   // stage 2 workgroup
+
+template <bool BF16>
+__device__ __forceinline__ void sqn_chunk(const void* g, long long n, long long i0, float (&acc)[8]) {
+  if (i0 >= n) return;
+  if (BF16) {
+    const uint16_t* gb = reinterpret_cast<const uint16_t*>(g);
+    if (i0 + 8 <= n && (((uintptr_t)(gb + i0)) & 15) == 0) {
+      const uint4 gv = *reinterpret_cast<const uint4*>(gb + i0);
+      const uint16_t* gs = reinterpret_cast<const uint16_t*>(&gv);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const float x = bf2f(gs[j]);
+        acc[j] = fmaf(x, x, acc[j]);
+      }
+    } else {
+      for (int j = 0; j < 8 && i0 + j < n; ++j) {
+        const float x = bf2f(gb[i0 + j]);
+        acc[j] = fmaf(x, x, acc[j]);
+      }
+    }
+  } else {
+    const float* gf = reinterpret_cast<const float*>(g);
+    if (i0 + 8 <= n && (((uintptr_t)(gf + i0)) & 15) == 0) {
+      const float4 a = reinterpret_cast<const float4*>(gf + i0)[0], b = reinterpret_cast<const float4*>(gf + i0)[1];
+      const float x[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+#pragma unroll
+      for (int j = 0; j < 8; ++j) acc[j] = fmaf(x[j], x[j], acc[j]);
+    } else {
+      for (int j = 0; j < 8 && i0 + j < n; ++j) {
+        const float x = gf[i0 + j];
+        acc[j] = fmaf(x, x, acc[j]);
+      }
+    }
+  }
+}
+
+template <bool BF16>
+__global__ __launch_bounds__(256) void k_grad_sqnorm_multi(const char* __restrict__ ts, int stride,
+                                                           const int* __restrict__ chunk_start, int ntensors,
+                                                           float* __restrict__ partials) {
+  const int total = chunk_start[ntensors];
+  const int c0 = blockIdx.x * SQN_CPB;
+  const int c1 = min(c0 + SQN_CPB, total);
+  float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  if (c0 < c1) {
+    int lo = 0, hi = ntensors - 1;  // last tensor whose first chunk is <= c0 (empty tensors are skipped)
+    while (lo < hi) {
+      const int mid = (lo + hi + 1) >> 1;
+      if (chunk_start[mid] <= c0) lo = mid; else hi = mid - 1;
+    }
+    int t = lo, c = c0;
+    while (c < c1) {
+      while (chunk_start[t + 1] <= c) ++t;  // c < total = chunk_start[ntensors]: t stays < ntensors
+      const char* rec = ts + (size_t)t * stride;
+      const void* g = *reinterpret_cast<const void* const*>(rec + sizeof(void*));
+      const long long n = *reinterpret_cast<const long long*>(rec + stride - sizeof(long long));
+      const int cend = min(c1, chunk_start[t + 1]);
+      long long i0 = (long long)(c - chunk_start[t]) * SQN_CHUNK + (long long)threadIdx.x * 8;
+      // whole chunks of an aligned tensor: branch-free loads, four chunks in
+      // flight per thread (same additions in the same order as sqn_chunk)
+      const int cfull = (((uintptr_t)g) & 15) == 0 ? min(cend, chunk_start[t] + (int)(n / SQN_CHUNK)) : c;
+      for (; c + 4 <= cfull; c += 4, i0 += 4 * SQN_CHUNK) {
+        if (BF16) {
+          const uint16_t* gb = reinterpret_cast<const uint16_t*>(g) + i0;
+          uint4 v[4];
+#pragma unroll
+          for (int u = 0; u < 4; ++u) v[u] = *reinterpret_cast<const uint4*>(gb + u * SQN_CHUNK);
+#pragma unroll
+          for (int u = 0; u < 4; ++u) {
+            const uint16_t* gs = reinterpret_cast<const uint16_t*>(&v[u]);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+              const float x = bf2f(gs[j]);
+              acc[j] = fmaf(x, x, acc[j]);
+            }
+          }
+        } else {
+          const float* gf = reinterpret_cast<const float*>(g) + i0;
+          float4 v[8];
+#pragma unroll
+          for (int u = 0; u < 4; ++u) {
+            v[2 * u] = reinterpret_cast<const float4*>(gf + u * SQN_CHUNK)[0];
+            v[2 * u + 1] = reinterpret_cast<const float4*>(gf + u * SQN_CHUNK)[1];
+          }
+#pragma unroll
+          for (int u = 0; u < 4; ++u) {
+            const float x[8] = {v[2 * u].x, v[2 * u].y, v[2 * u].z, v[2 * u].w,
+                                v[2 * u + 1].x, v[2 * u + 1].y, v[2 * u + 1].z, v[2 * u + 1].w};
+#pragma unroll
+            for (int j = 0; j < 8; ++j) acc[j] = fmaf(x[j], x[j], acc[j]);
+          }
+        }
+      }
+      for (; c < cend; ++c, i0 += SQN_CHUNK) sqn_chunk<BF16>(g, n, i0, acc);
+    }
+  }
+  float s = ((acc[0] + acc[1]) + (acc[2] + acc[3])) + ((acc[4] + acc[5]) + (acc[6] + acc[7]));
+  s = wave_sum(s);
+  __shared__ float ws[4];
+  if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) partials[blockIdx.x] = ((ws[0] + ws[1]) + ws[2]) + ws[3];
+}
+
+// rec[0] = gscale * sqrt(sum)  (norm of the MEAN gradient: the buffers hold the sum over ranks)
+// rec[1] = min(1, max_norm / (rec[0] + 1e-6)), NaN kept as torch.clamp(max=1) keeps it
+__global__ __launch_bounds__(FIN_THREADS) void k_grad_norm_finalize(const float* __restrict__ partials, int n,
+                                                                    float gscale, float max_norm,
+                                                                    float* __restrict__ rec) {
+  float s = 0.f;
+  for (int i = threadIdx.x; i < n; i += FIN_THREADS) s += partials[i];
+  s = wave_sum(s);
+  __shared__ float ws[FIN_THREADS / 64];
+  if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float tot = ws[0];
+    for (int w = 1; w < FIN_THREADS / 64; ++w) tot += ws[w];
+    const float norm = gscale * sqrtf(tot);
+    const float c = max_norm / (norm + 1e-6f);
+    rec[0] = norm;
+    rec[1] = c > 1.f ? 1.f : c;
   }
 }
 
@@ -123,18 +286,55 @@ __global__ __launch_bounds__(256) void k_bf16_to_f32(const uint16_t* __restrict_
 
 PTO_API int pto_adamw_block_count(long long n) { return (int)((n + ADAM_CHUNK - 1) / ADAM_CHUNK); }
 
+// The reduction's shape, for callers sizing buffers and for the tests' error bound.
+PTO_API int pto_grad_sqnorm_chunks(long long n) { return (int)((n + SQN_CHUNK - 1) / SQN_CHUNK); }
+PTO_API int pto_grad_sqnorm_blocks(long long chunks) { return (int)((chunks + SQN_CPB - 1) / SQN_CPB); }
+PTO_API int pto_grad_sqnorm_chunks_per_block(void) { return SQN_CPB; }
+PTO_API int pto_grad_norm_finalize_threads(void) { return FIN_THREADS; }
+
+// pto_adamw_multi with the gradient scale multiplied by *gscale_ptr (device
+// memory: the clip coefficient of pto_grad_norm_finalize); nullptr: gscale alone.
+PTO_API int pto_adamw_multi_clip(const AdamTensor* ts, const int* block_start, int ntensors, int nblocks, int mixed,
+                                 const float* lr_ptr, float lr, float beta1, float beta2, float eps, float wd,
+                                 int step, float gscale, const float* gscale_ptr, int zero_grad, hipStream_t s) {
+  if (nblocks <= 0) return 0;
+  AdamHyper h{lr, beta1, beta2, eps, wd, 1.f - powf(beta1, (float)step), 1.f - powf(beta2, (float)step), gscale};
+  auto k = mixed ? (gscale_ptr ? k_adamw_multi<true, true> : k_adamw_multi<true, false>)
+                 : (gscale_ptr ? k_adamw_multi<false, true> : k_adamw_multi<false, false>);
+  hipLaunchKernelGGL(k, dim3(nblocks), dim3(256), 0, s, ts, block_start, ntensors, lr_ptr, h, zero_grad, gscale_ptr);
+  return (int)hipGetLastError();
+}
+
 // step = 1-based optimizer step (bias corrections computed here).
 PTO_API int pto_adamw_multi(const AdamTensor* ts, const int* block_start, int ntensors, int nblocks, int mixed,
                             const float* lr_ptr, float lr, float beta1, float beta2, float eps, float wd, int step,
                             float gscale, int zero_grad, hipStream_t s) {
-  if (nblocks <= 0) return 0;
-  AdamHyper h{lr, beta1, beta2, eps, wd, 1.f - powf(beta1, (float)step), 1.f - powf(beta2, (float)step), gscale};
-  if (mixed)
-    hipLaunchKernelGGL(k_adamw_multi<true>, dim3(nblocks), dim3(256), 0, s, ts, block_start, ntensors, lr_ptr, h,
-                       zero_grad);
+  return pto_adamw_multi_clip(ts, block_start, ntensors, nblocks, mixed, lr_ptr, lr, beta1, beta2, eps, wd, step,
+                              gscale, nullptr, zero_grad, s);
+}
+
+// Stage 1 of the gradient norm.  ts: device table of `stride`-byte records
+// (AdamTensor / SgdTensor); chunk_start: ntensors + 1 device ints, prefix of
+// pto_grad_sqnorm_chunks(n); partials: nblocks = pto_grad_sqnorm_blocks(total
+// chunks) floats, every one of them written.
+PTO_API int pto_grad_sqnorm_multi(const void* ts, int stride, const int* chunk_start, int ntensors, int bf16,
+                                  float* partials, int nblocks, hipStream_t s) {
+  if (nblocks <= 0 || ntensors <= 0) return 0;
+  if (stride < (int)(sizeof(void*) * 2 + sizeof(long long))) return (int)hipErrorInvalidValue;
+  const char* t = reinterpret_cast<const char*>(ts);
+  if (bf16)
+    hipLaunchKernelGGL(k_grad_sqnorm_multi<true>, dim3(nblocks), dim3(256), 0, s, t, stride, chunk_start, ntensors,
+                       partials);
   else
-    hipLaunchKernelGGL(k_adamw_multi<false>, dim3(nblocks), dim3(256), 0, s, ts, block_start, ntensors, lr_ptr, h,
-                       zero_grad);
+    hipLaunchKernelGGL(k_grad_sqnorm_multi<false>, dim3(nblocks), dim3(256), 0, s, t, stride, chunk_start, ntensors,
+                       partials);
+  return (int)hipGetLastError();
+}
+
+// Stage 2: rec[0] = gscale * sqrt(sum of the n partials), rec[1] = clip coefficient.
+PTO_API int pto_grad_norm_finalize(const float* partials, int n, float gscale, float max_norm, float* rec,
+                                   hipStream_t s) {
+  hipLaunchKernelGGL(k_grad_norm_finalize, dim3(1), dim3(FIN_THREADS), 0, s, partials, n, gscale, max_norm, rec);
   return (int)hipGetLastError();
 }
 

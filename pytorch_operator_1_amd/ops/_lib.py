@@ -123,6 +123,15 @@ _SIGS = {
     "pto_adamw_block_count": [_L],
     "pto_adamw_multi": [_P, _P, _I, _I, _I, _P, _F, _F, _F, _F, _F, _I, _F, _I, _P],
     "pto_bf16_to_f32": [_P, _P, _L, _P],
+    # global gradient norm + clip coefficient on the device (optim_kernels.hip)
+    "pto_grad_sqnorm_chunks": [_L],
+    "pto_grad_sqnorm_blocks": [_L],
+    "pto_grad_sqnorm_chunks_per_block": [],
+    "pto_grad_norm_finalize_threads": [],
+    "pto_grad_sqnorm_multi": [_P, _I, _P, _I, _I, _P, _I, _P],
+    "pto_grad_norm_finalize": [_P, _I, _F, _F, _P, _P],
+    "pto_adamw_multi_clip": [_P, _P, _I, _I, _I, _P, _F, _F, _F, _F, _F, _I, _F, _P, _I, _P],
+    "pto_sgd_multi_clip": [_P, _P, _I, _I, _P, _F, _F, _F, _F, _P, _I, _I, _P, _L, _P],
     # LLM memory-bound kernels (csrc/kernels/llm_kernels.hip)
     "pto_add_rmsnorm_fwd": [_P, _P, _P, _P, _P, _P, _L, _I, _F, _P],
     "pto_rmsnorm_bwd_groups": [_L],

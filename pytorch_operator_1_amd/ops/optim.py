@@ -49,6 +49,65 @@ class _TableMixin:
         self._gptrs = _grad_ptrs(self.param_groups)
 
 
+class _GradNormMixin:
+    """Global gradient norm and clip coefficient, computed on the device
+    (csrc/kernels/optim_kernels.hip): one read-only pass per param group
+    writes per-workgroup partial sums of squares, ONE single-workgroup launch
+    reduces all of them to ``{grad_norm, clip_coef}``, and the optimizer
+    kernel scales the gradients by the coefficient it reads from device
+    memory, in the one read of the gradient it already does.  No host sync, no rewrite of the gradients, and every
+    addition happens in an order fixed by the parameter shapes alone, so DDP
+    replicas holding identical gradients derive a bit-identical coefficient.
+
+    ``grad_norm`` (norm of the mean gradient, before clipping) and
+    ``clip_coef`` are 1-element fp32 device tensors after a step with
+    ``max_grad_norm``; reading them is the caller's decision to sync."""
+
+    grad_norm: torch.Tensor | None = None
+    clip_coef: torch.Tensor | None = None
+    _norm_key = None
+
+    def _norm_setup(self):
+        """Chunk-prefix tables, partials and the record.  They depend on the
+        parameter shapes only, so they survive a rebuild of the launch tables."""
+        key = tuple(tuple(p.numel() for p in g["params"]) for g in self.param_groups)
+        if self._norm_key == key:
+            return
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("call prepare_capture(max_grad_norm=...) before capturing a clipped step()")
+        L = _lib.lib()
+        dev = self.param_groups[0]["params"][0].device
+        plans, off = [], 0
+        for numels in key:
+            cs = [0]
+            for n in numels:
+                cs.append(cs[-1] + L.pto_grad_sqnorm_chunks(n))
+            nb = L.pto_grad_sqnorm_blocks(cs[-1])
+            plans.append((_upload(torch.tensor(cs, dtype=torch.int32), dev), nb, off))
+            off += nb  # each group's partials: a disjoint range
+        self._norm_plans = plans
+        self._partials = torch.empty(max(off, 1), dtype=torch.float32, device=dev)
+        self._rec = torch.zeros(2, dtype=torch.float32, device=dev)
+        self.grad_norm, self.clip_coef = self._rec[0:1], self._rec[1:2]
+        self._norm_key = key
+
+    def _grad_norm_launch(self, tables, grad_scale: float, max_grad_norm: float) -> int:
+        """``tables``: per group ``(record table address, record bytes,
+        ntensors, grads are bf16)`` of the REFRESHED launch tables.  Returns
+        the device address of the coefficient."""
+        if not max_grad_norm >= 0:
+            raise ValueError(f"max_grad_norm must be >= 0, got {max_grad_norm}")
+        self._norm_setup()
+        L, s, total = _lib.lib(), _lib.stream_ptr(), 0
+        for (tptr, stride, nt, bf16), (cs, nb, off) in zip(tables, self._norm_plans):
+            _lib.check(L.pto_grad_sqnorm_multi(tptr, stride, cs.data_ptr(), nt, int(bf16),
+                                               self._partials.data_ptr() + 4 * off, nb, s), "grad_sqnorm_multi")
+            total = off + nb
+        _lib.check(L.pto_grad_norm_finalize(self._partials.data_ptr(), total, float(grad_scale),
+                                            float(max_grad_norm), self._rec.data_ptr(), s), "grad_norm_finalize")
+        return self._rec.data_ptr() + 4
+
+
 def _upload(host: torch.Tensor, device) -> torch.Tensor:
     """Host -> device copy of a launch table that never blocks the host: a
     table is rebuilt whenever autograd hands over gradients at new addresses
@@ -111,10 +170,19 @@ class SgdTable:
         self.starts = _to_device(torch.tensor(starts, dtype=torch.int32), device, pending, reserved)
 
     def step(self, lr_dev, lr, momentum, weight_decay, grad_scale, nesterov, zero_grad=True, stream=None,
-             batch_cursor=None, n_batches=1):
+             batch_cursor=None, n_batches=1, gscale_ptr: int | None = None):
         """``batch_cursor``: optional int64 device scalar advanced modulo
-        ``n_batches`` by the same launch (fused trainer data cursor)."""
+        ``n_batches`` by the same launch (fused trainer data cursor).
+        ``gscale_ptr``: device address of a float multiplied into
+        ``grad_scale`` by the kernel (the clip coefficient)."""
         s = stream if stream is not None else _lib.stream_ptr()
+        if gscale_ptr is not None:
+            _lib.check(self.L.pto_sgd_multi_clip(self.table.data_ptr(), self.starts.data_ptr(), self.ntensors,
+                                                 self.nblocks, None if lr_dev is None else lr_dev.data_ptr(),
+                                                 float(lr), float(momentum), float(weight_decay), float(grad_scale),
+                                                 gscale_ptr, int(bool(nesterov)), int(bool(zero_grad)),
+                                                 _lib.ptr(batch_cursor), int(n_batches), s), "sgd_multi_clip")
+            return
         _lib.check(self.L.pto_sgd_multi(self.table.data_ptr(), self.starts.data_ptr(), self.ntensors, self.nblocks,
                                         None if lr_dev is None else lr_dev.data_ptr(), float(lr), float(momentum),
                                         float(weight_decay), float(grad_scale), int(bool(nesterov)),
@@ -122,11 +190,17 @@ class SgdTable:
                    "sgd_multi")
 
 
-class FusedSGD(_TableMixin, torch.optim.Optimizer):
+class FusedSGD(_TableMixin, _GradNormMixin, torch.optim.Optimizer):
     """Drop-in ``torch.optim.SGD`` (dampening=0) backed by one HIP launch.
 
     Grads are consumed and zeroed in the same launch when ``zero_grad=True``
     is passed to :meth:`step` (set_to_none semantics are emulated by zeros).
+
+    ``step(max_grad_norm=x)`` clips the global norm of the (scaled) gradients
+    to ``x`` like ``torch.nn.utils.clip_grad_norm_`` (``inf``: only report
+    the norm), see :class:`_GradNormMixin`.  In a captured step
+    ``max_grad_norm`` is fixed at capture, like momentum; norm and
+    coefficient are recomputed by every replay from that replay's gradients.
     """
 
     def __init__(self, params, lr=0.01, momentum=0.0, weight_decay=0.0, nesterov=False):
@@ -155,9 +229,13 @@ class FusedSGD(_TableMixin, torch.optim.Optimizer):
             self._tables.append(SgdTable(triples, dev, keep_grads=False, pending=self._pending,
                                          reserved=self._reserved))
 
-    def prepare_capture(self):
+    def prepare_capture(self, max_grad_norm: float | None = None):
         """Before capturing :meth:`step` into a HIP graph: allocate (outside
-        the graph's memory pool) the launch tables the captured step will use."""
+        the graph's memory pool) the launch tables the captured step will
+        use and, when it will clip (``max_grad_norm`` as passed to the
+        captured :meth:`step`), the partials and the norm record."""
+        if max_grad_norm is not None:
+            self._norm_setup()
         self._reserved = []
         self._lr_dev, self._lr_host = [], []
         for group in self.param_groups:
@@ -187,16 +265,21 @@ class FusedSGD(_TableMixin, torch.optim.Optimizer):
         self._reserved = []
 
     @torch.no_grad()
-    def step(self, closure=None, grad_scale: float = 1.0, zero_grad: bool = False):
+    def step(self, closure=None, grad_scale: float = 1.0, zero_grad: bool = False,
+             max_grad_norm: float | None = None):
         loss = None
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
         self._refresh()
         capturing = self._lr_dev is not None and torch.cuda.is_current_stream_capturing()
+        coef = None
+        if max_grad_norm is not None:  # reads the gradients before the update zeroes them
+            coef = self._grad_norm_launch([(t.table.data_ptr(), ctypes.sizeof(_SgdTensor), t.ntensors, False)
+                                           for t in self._tables], grad_scale, max_grad_norm)
         for i, (group, table) in enumerate(zip(self.param_groups, self._tables)):
             table.step(self._lr_dev[i] if capturing else None, group["lr"], group["momentum"],
-                       group["weight_decay"], grad_scale, group["nesterov"], zero_grad=zero_grad)
+                       group["weight_decay"], grad_scale, group["nesterov"], zero_grad=zero_grad, gscale_ptr=coef)
         return loss
 
     def zero_grad(self, set_to_none: bool = False):
@@ -212,7 +295,7 @@ class _AdamTensor(ctypes.Structure):
                 ("v", ctypes.c_void_p), ("n", ctypes.c_longlong)]
 
 
-class FusedAdamW(_TableMixin, torch.optim.Optimizer):
+class FusedAdamW(_TableMixin, _GradNormMixin, torch.optim.Optimizer):
     """Multi-tensor AdamW in one HIP launch (csrc/kernels/optim_kernels.hip).
 
     bf16 parameters get fp32 master weights and fp32 moments inside the
@@ -220,6 +303,11 @@ class FusedAdamW(_TableMixin, torch.optim.Optimizer):
     ``torch.optim.AdamW`` (decoupled weight decay, bias correction) up to
     the bf16 rounding of the exported parameter.  ``grad_scale`` folds a
     DDP 1/world (or loss-scale) factor into the same pass.
+
+    ``step(max_grad_norm=x)`` clips the global norm of the scaled gradients
+    (all param groups together) to ``x`` like
+    ``torch.nn.utils.clip_grad_norm_`` (``inf``: only report the norm), see
+    :class:`_GradNormMixin`.
     """
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2):
@@ -264,7 +352,8 @@ class FusedAdamW(_TableMixin, torch.optim.Optimizer):
                                  int(bool(mixed)), keep))
 
     @torch.no_grad()
-    def step(self, closure=None, grad_scale: float = 1.0, zero_grad: bool = False):
+    def step(self, closure=None, grad_scale: float = 1.0, zero_grad: bool = False,
+             max_grad_norm: float | None = None):
         loss = None
         if closure is not None:
             with torch.enable_grad():
@@ -272,8 +361,19 @@ class FusedAdamW(_TableMixin, torch.optim.Optimizer):
         self._refresh()
         self._step += 1
         L = _lib.lib()
+        coef = None
+        if max_grad_norm is not None:  # reads the gradients before the update zeroes them
+            coef = self._grad_norm_launch([(t[0].data_ptr(), ctypes.sizeof(_AdamTensor), t[2], t[4])
+                                           for t in self._tables], grad_scale, max_grad_norm)
         for group, (table, starts, nt, nb, mixed, _) in zip(self.param_groups, self._tables):
             b1, b2 = group["betas"]
+            if coef is not None:
+                _lib.check(L.pto_adamw_multi_clip(table.data_ptr(), starts.data_ptr(), nt, nb, mixed, None,
+                                                  float(group["lr"]), float(b1), float(b2), float(group["eps"]),
+                                                  float(group["weight_decay"]), self._step, float(grad_scale),
+                                                  coef, int(bool(zero_grad)), _lib.stream_ptr()),
+                           "adamw_multi_clip")
+                continue
             _lib.check(L.pto_adamw_multi(table.data_ptr(), starts.data_ptr(), nt, nb, mixed, None,
                                          float(group["lr"]), float(b1), float(b2), float(group["eps"]),
                                          float(group["weight_decay"]), self._step, float(grad_scale),

@@ -28,22 +28,44 @@ from ..utils.profiling import StepTimer
 
 class _TorchOpt:
     """Stock ``torch.optim`` behind the fused optimizers' ``step(grad_scale,
-    zero_grad)`` call (CPU runs: the HIP optimizers need a GPU)."""
+    zero_grad, max_grad_norm)`` call (CPU runs: the HIP optimizers need a
+    GPU).  Clipping is ``torch.nn.utils.clip_grad_norm_`` on the scaled
+    gradients; ``grad_norm`` / ``clip_coef`` as on the fused optimizers."""
 
     def __init__(self, opt):
         self.opt = opt
         self.state = opt.state
         self.param_groups = opt.param_groups
+        self.grad_norm = None
+        self.clip_coef = None
 
     @torch.no_grad()
-    def step(self, grad_scale: float = 1.0, zero_grad: bool = False):
+    def step(self, grad_scale: float = 1.0, zero_grad: bool = False, max_grad_norm: float | None = None):
         for g in self.param_groups:
             for p in g["params"]:
                 if p.grad is not None and grad_scale != 1.0:
                     p.grad.mul_(grad_scale)
+        if max_grad_norm is not None:
+            params = [p for g in self.param_groups for p in g["params"] if p.grad is not None]
+            total = torch.nn.utils.clip_grad_norm_(params, max_grad_norm, error_if_nonfinite=False)
+            self.grad_norm = total.detach().float().reshape(1)
+            self.clip_coef = torch.clamp(max_grad_norm / (self.grad_norm + 1e-6), max=1.0)
         self.opt.step()
         if zero_grad:
             self.opt.zero_grad(set_to_none=False)
+
+
+def _scalar(t):
+    """Host value of a 1-element tensor (a device sync), None before the first step."""
+    return None if t is None else float(t)
+
+
+def _clip_text(max_grad_norm):
+    if max_grad_norm is None:
+        return "off"
+    if max_grad_norm == float("inf"):
+        return "norm reported, not clipped"
+    return f"global grad norm clipped to {max_grad_norm:g} on the device"
 
 
 class CheckpointMixin:
@@ -110,7 +132,7 @@ class ResNetTrainer(CheckpointMixin):
 
     def __init__(self, device, batch_size: int = 256, image_size: int = 224, lr: float = 0.1,
                  momentum: float = 0.9, weight_decay: float = 1e-4, seed: int = 0, bucket_mb: float | None = None,
-                 force_ddp: bool = False, graph: bool | None = None):
+                 force_ddp: bool = False, graph: bool | None = None, max_grad_norm: float | None = None):
         from ..models.resnet import resnet50, synthetic_images
 
         torch.manual_seed(seed)
@@ -119,6 +141,7 @@ class ResNetTrainer(CheckpointMixin):
         torch.backends.cudnn.benchmark = True
         self.device = device
         self.batch_size = batch_size
+        self.max_grad_norm = max_grad_norm  # global-norm clip (inf: report only); fixed once a step is captured
         self.model = resnet50().to(device=device, memory_format=torch.channels_last)
         self.model.train()
         self.bucketer = GradBucketer(self.model, bucket_mb=bucket_mb, force_ddp=force_ddp)
@@ -156,7 +179,7 @@ class ResNetTrainer(CheckpointMixin):
         capturing: :meth:`step` replays it right after)."""
         torch.cuda.synchronize(self.device)
         self.bucketer.release()  # grads None: the captured backward allocates them in the graph's pool
-        self.opt.prepare_capture()
+        self.opt.prepare_capture(max_grad_norm=self.max_grad_norm)
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g):
             with torch.autocast(device_type="cuda", dtype=torch.bfloat16):
@@ -165,7 +188,8 @@ class ResNetTrainer(CheckpointMixin):
             loss.backward()
             GradStash.assert_drained()
             self.bucketer.finish()
-            self.opt.step(grad_scale=self.bucketer.grad_scale, zero_grad=self.bucketer.optimizer_zeroes_grads)
+            self.opt.step(grad_scale=self.bucketer.grad_scale, zero_grad=self.bucketer.optimizer_zeroes_grads,
+                          max_grad_norm=self.max_grad_norm)
         self.opt.finish_capture()  # the launch table of the graph's gradients
         self._loss = loss.detach()
         self._graph = g
@@ -182,7 +206,8 @@ class ResNetTrainer(CheckpointMixin):
         with t.phase("allreduce_wait"):
             self.bucketer.finish()
         with t.phase("optimizer"):
-            self.opt.step(grad_scale=self.bucketer.grad_scale, zero_grad=self.bucketer.optimizer_zeroes_grads)
+            self.opt.step(grad_scale=self.bucketer.grad_scale, zero_grad=self.bucketer.optimizer_zeroes_grads,
+                          max_grad_norm=self.max_grad_norm)
             self.bucketer.release()
         self._loss = loss.detach()
         self.steps_done += 1
@@ -194,6 +219,12 @@ class ResNetTrainer(CheckpointMixin):
     def last_loss(self):
         return None if self._loss is None else float(self._loss)
 
+    def last_grad_norm(self):
+        return _scalar(self.opt.grad_norm) if self.max_grad_norm is not None else None
+
+    def last_clip_coef(self):
+        return _scalar(self.opt.clip_coef) if self.max_grad_norm is not None else None
+
     def samples_per_step(self) -> int:
         return self.batch_size
 
@@ -201,13 +232,15 @@ class ResNetTrainer(CheckpointMixin):
         return {"model": "resnet50 (v1.5, 25.6M params)", "input_shape": [3, 224, 224],
                 "optimizer": "SGD momentum=0.9 wd=1e-4 (FusedSGD HIP)", "amp": "bf16 autocast, fp32 master",
                 "step": (f"whole step replayed as one HIP graph (after {self.EAGER_STEPS} eager steps)"
-                         if self.use_graph else "eager")}
+                         if self.use_graph else "eager"),
+                "grad_clip": _clip_text(self.max_grad_norm)}
 
 
 class LlamaTrainer(CheckpointMixin):
     def __init__(self, device, model: str = "llama3-8b", batch_size: int = 2, seq_len: int = 4096,
                  lr: float = 3e-4, weight_decay: float = 0.1, seed: int = 0, checkpoint: str = "none",
-                 impl: str | None = None, bucket_mb: float | None = None, force_ddp: bool = False):
+                 impl: str | None = None, bucket_mb: float | None = None, force_ddp: bool = False,
+                 max_grad_norm: float | None = None):
         from ..models.llama import CONFIGS, Llama, synthetic_tokens
 
         torch.manual_seed(seed)
@@ -216,6 +249,7 @@ class LlamaTrainer(CheckpointMixin):
         self.name = model
         self.device = device
         self.batch_size, self.seq_len = batch_size, seq_len
+        self.max_grad_norm = max_grad_norm  # global-norm clip (the Llama recipe: 1.0; inf: report only)
         self.model = Llama(self.cfg, impl=impl, device=device, checkpoint=checkpoint)
         self.model.train()
         # W^T copies for K-contiguous dgrad GEMMs (PTO_WT=0: plain F.linear backward;
@@ -244,7 +278,8 @@ class LlamaTrainer(CheckpointMixin):
         with t.phase("allreduce_wait"):
             self.bucketer.finish()
         with t.phase("optimizer"):
-            self.opt.step(grad_scale=self.bucketer.grad_scale, zero_grad=self.bucketer.optimizer_zeroes_grads)
+            self.opt.step(grad_scale=self.bucketer.grad_scale, zero_grad=self.bucketer.optimizer_zeroes_grads,
+                          max_grad_norm=self.max_grad_norm)
             self.bucketer.release()
             if self.transposed_dgrad:
                 self.model.refresh_transposed()
@@ -258,6 +293,12 @@ class LlamaTrainer(CheckpointMixin):
     def last_loss(self):
         return None if self._loss is None else float(self._loss)
 
+    def last_grad_norm(self):
+        return _scalar(self.opt.grad_norm) if self.max_grad_norm is not None else None
+
+    def last_clip_coef(self):
+        return _scalar(self.opt.clip_coef) if self.max_grad_norm is not None else None
+
     def samples_per_step(self) -> int:
         return self.batch_size * self.seq_len  # tokens
 
@@ -269,4 +310,5 @@ class LlamaTrainer(CheckpointMixin):
                 "optimizer": "AdamW betas=(0.9,0.95) wd=0.1 (FusedAdamW HIP, fp32 master/m/v)",
                 "amp": "bf16 params/activations, fp32 optimizer state",
                 "checkpoint": self.model.checkpoint,
-                "dgrad": "W^T copies (K-contiguous dX GEMMs)" if self.transposed_dgrad else "F.linear"}
+                "dgrad": "W^T copies (K-contiguous dX GEMMs)" if self.transposed_dgrad else "F.linear",
+                "grad_clip": _clip_text(self.max_grad_norm)}

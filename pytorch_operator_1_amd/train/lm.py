@@ -57,7 +57,13 @@ def parse_args(argv=None):
     p.add_argument("--fail-at-step", type=int, default=int(os.environ.get("PTO_FAIL_AT_STEP", "0")),
                    help="fault injection: SIGKILL self before this step (first incarnation only)")
     p.add_argument("--fail-rank", type=int, default=int(os.environ.get("PTO_FAIL_RANK", "0")))
-    return p.parse_args(argv)
+    p.add_argument("--max-grad-norm", type=float, default=None,
+                   help="clip the global gradient norm to this value on the device and log it "
+                        "(inf: log the norm without clipping; default: off)")
+    args = p.parse_args(argv)
+    if args.max_grad_norm is not None and not args.max_grad_norm >= 0:
+        p.error("--max-grad-norm must be >= 0")
+    return args
 
 
 def build(args, device):
@@ -66,10 +72,11 @@ def build(args, device):
     if args.model == "resnet50":
         kw = {} if args.lr is None else {"lr": args.lr}
         return ResNetTrainer(device, batch_size=args.batch_size or 64, image_size=args.image_size, seed=args.seed,
-                             **kw)
+                             max_grad_norm=args.max_grad_norm, **kw)
     kw = {} if args.lr is None else {"lr": args.lr}
     return LlamaTrainer(device, model=args.model, batch_size=args.batch_size or 2, seq_len=args.seq_len,
-                        seed=args.seed, checkpoint=args.activation_checkpoint, **kw)
+                        seed=args.seed, checkpoint=args.activation_checkpoint, max_grad_norm=args.max_grad_norm,
+                        **kw)
 
 
 def _main(argv=None):
@@ -110,9 +117,13 @@ def _main(argv=None):
             loss = trainer.last_loss()
             now = time.time()
             sps = steps_since * trainer.samples_per_step() * world / max(now - t_last, 1e-9)
-            print(f"step {done}/{args.steps}\tloss={loss:.6f}\t{sps:.1f} samples/s", flush=True)
+            clip, extra = "", {}
+            if args.max_grad_norm is not None:  # read here only: last_loss() has already synced
+                extra = {"grad_norm": trainer.last_grad_norm(), "clip_coef": trainer.last_clip_coef()}
+                clip = f"\tgrad_norm={extra['grad_norm']:.4f}"
+            print(f"step {done}/{args.steps}\tloss={loss:.6f}{clip}\t{sps:.1f} samples/s", flush=True)
             metrics.emit(event="train", step=done, loss=loss, samples_per_sec=round(sps, 1),
-                         step_seconds=(now - t_last) / steps_since, rank=rank)
+                         step_seconds=(now - t_last) / steps_since, rank=rank, **extra)
             t_last, steps_since = now, 0
         if saver and args.checkpoint_interval and done % args.checkpoint_interval == 0 and done < args.steps:
             saver.save(done, trainer.checkpoint_tensors(), trainer.checkpoint_meta())

@@ -23,6 +23,14 @@ struct AdamTensor {
   long long n;
 };
 
+// record of k_grad_accum_multi (micro-batch gradient accumulation, below)
+struct AccumTensor {
+  const void* g;  // gradient of this micro-batch: bf16 or fp32; nullptr = none
+  float* acc;     // fp32 running sum
+  void* out;      // FOLD only: destination in the gradient's dtype
+  long long n;
+};
+
 namespace {
 
 constexpr int ADAM_CHUNK = 256 * 8;  // elements per block (8 per thread)
@@ -274,6 +282,98 @@ __global__ __launch_bounds__(FIN_THREADS) void k_grad_norm_finalize(const float*
   }
 }
 
+// ---- micro-batch gradient accumulation in fp32 ---------------------------
+//
+// One optimizer step over N micro-batches sums their gradients in an fp32
+// accumulator per parameter (a bf16 running sum of magnitude 256 no longer
+// sees an addend of 1).  One launch per table, k_adamw_multi's layout: a
+// record per tensor, block_start[t] the first block of tensor t, ACC_CHUNK
+// elements per block, 8 per thread.
+//   ACC_INIT  acc = float(g)                 first micro-batch: no zeroing pass
+//   ACC_ADD   acc = acc + float(g)           one fp32 add
+//   ACC_FOLD  out = cast(acc + float(g))     last micro-batch; acc is NOT written
+// cast is f2bf for bf16 gradients, the identity for fp32.  out may be g itself
+// (every thread reads its 8 elements before it writes them) or another buffer
+// (a bucket slot).  g == nullptr is a parameter without a gradient in this
+// micro-batch, g = 0: INIT writes zeros, ADD does nothing, FOLD writes
+// cast(acc).  Plain vector stores, no atomics: the result is a pure function
+// of the inputs.  Mode and dtype are template parameters for the reason given
+// above k_adamw_multi.
+constexpr int ACC_CHUNK = 256 * 8;  // elements per block (8 per thread)
+enum { ACC_INIT = 0, ACC_ADD = 1, ACC_FOLD = 2 };
+
+template <bool BF16>
+__device__ __forceinline__ void acc_load_g(const void* g, long long i0, float (&x)[8]) {
+  if (BF16) {
+    const uint4 gv = *reinterpret_cast<const uint4*>(reinterpret_cast<const uint16_t*>(g) + i0);
+    const uint16_t* gs = reinterpret_cast<const uint16_t*>(&gv);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) x[j] = bf2f(gs[j]);
+  } else {
+    const float4* gp = reinterpret_cast<const float4*>(reinterpret_cast<const float*>(g) + i0);
+    const float4 a = gp[0], b = gp[1];
+    x[0] = a.x; x[1] = a.y; x[2] = a.z; x[3] = a.w; x[4] = b.x; x[5] = b.y; x[6] = b.z; x[7] = b.w;
+  }
+}
+
+template <bool BF16, int MODE>
+__global__ __launch_bounds__(256) void k_grad_accum_multi(const AccumTensor* __restrict__ ts,
+                                                          const int* __restrict__ block_start, int ntensors) {
+  int lo = 0, hi = ntensors - 1;
+  const int bid = blockIdx.x;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (block_start[mid] <= bid) lo = mid; else hi = mid - 1;
+  }
+  const AccumTensor t = ts[lo];
+  const long long i0 = (long long)(bid - block_start[lo]) * ACC_CHUNK + (long long)threadIdx.x * 8;
+  if (i0 >= t.n) return;
+  const bool has_g = t.g != nullptr;  // uniform over the block
+  if (MODE == ACC_ADD && !has_g) return;
+  constexpr int GB = BF16 ? 2 : 4;  // bytes per gradient element
+  uintptr_t addr = (uintptr_t)(t.acc + i0);
+  if (has_g) addr |= (uintptr_t)t.g + (uintptr_t)i0 * GB;
+  if (MODE == ACC_FOLD) addr |= (uintptr_t)t.out + (uintptr_t)i0 * GB;
+  if (i0 + 8 <= t.n && (addr & 15) == 0) {
+    float x[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    if (has_g) acc_load_g<BF16>(t.g, i0, x);
+    float4* ap = reinterpret_cast<float4*>(t.acc + i0);
+    if (MODE != ACC_INIT) {
+      const float4 a = ap[0], b = ap[1];
+      const float s[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+      if (has_g) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) x[j] = s[j] + x[j];
+      } else {  // FOLD without a gradient: cast(acc), not acc + 0 (keeps -0)
+#pragma unroll
+        for (int j = 0; j < 8; ++j) x[j] = s[j];
+      }
+    }
+    if (MODE != ACC_FOLD) {
+      ap[0] = float4{x[0], x[1], x[2], x[3]};
+      ap[1] = float4{x[4], x[5], x[6], x[7]};
+    } else if (BF16) {
+      uint16_t o[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) o[j] = f2bf(x[j]);
+      *reinterpret_cast<uint4*>(reinterpret_cast<uint16_t*>(t.out) + i0) = *reinterpret_cast<const uint4*>(o);
+    } else {
+      float4* op = reinterpret_cast<float4*>(reinterpret_cast<float*>(t.out) + i0);
+      op[0] = float4{x[0], x[1], x[2], x[3]};
+      op[1] = float4{x[4], x[5], x[6], x[7]};
+    }
+  } else {
+    for (long long e = i0; e < i0 + 8 && e < t.n; ++e) {
+      float x = 0.f;
+      if (has_g) x = BF16 ? bf2f(reinterpret_cast<const uint16_t*>(t.g)[e]) : reinterpret_cast<const float*>(t.g)[e];
+      if (MODE != ACC_INIT) x = has_g ? t.acc[e] + x : t.acc[e];
+      if (MODE != ACC_FOLD) t.acc[e] = x;
+      else if (BF16) reinterpret_cast<uint16_t*>(t.out)[e] = f2bf(x);
+      else reinterpret_cast<float*>(t.out)[e] = x;
+    }
+  }
+}
+
 // bf16 <-> fp32 flat casts (master-weight init, checkpoint export)
 __global__ __launch_bounds__(256) void k_bf16_to_f32(const uint16_t* __restrict__ x, float* __restrict__ y, long long n) {
   const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
@@ -335,6 +435,26 @@ PTO_API int pto_grad_sqnorm_multi(const void* ts, int stride, const int* chunk_s
 PTO_API int pto_grad_norm_finalize(const float* partials, int n, float gscale, float max_norm, float* rec,
                                    hipStream_t s) {
   hipLaunchKernelGGL(k_grad_norm_finalize, dim3(1), dim3(FIN_THREADS), 0, s, partials, n, gscale, max_norm, rec);
+  return (int)hipGetLastError();
+}
+
+PTO_API int pto_grad_accum_block_count(long long n) { return (int)((n + ACC_CHUNK - 1) / ACC_CHUNK); }
+
+// fp32 micro-batch accumulation over a device table of AccumTensor records.
+// block_start: ntensors device ints, prefix of pto_grad_accum_block_count(n);
+// bf16: the gradients' (and FOLD's out) dtype; mode: 0 INIT, 1 ADD, 2 FOLD.
+PTO_API int pto_grad_accum_multi(const AccumTensor* ts, const int* block_start, int ntensors, int nblocks, int bf16,
+                                 int mode, hipStream_t s) {
+  if (mode < ACC_INIT || mode > ACC_FOLD) return (int)hipErrorInvalidValue;
+  if (nblocks <= 0 || ntensors <= 0) return 0;
+  void (*k)(const AccumTensor*, const int*, int);
+  if (bf16)
+    k = mode == ACC_INIT ? k_grad_accum_multi<true, ACC_INIT>
+      : mode == ACC_ADD  ? k_grad_accum_multi<true, ACC_ADD> : k_grad_accum_multi<true, ACC_FOLD>;
+  else
+    k = mode == ACC_INIT ? k_grad_accum_multi<false, ACC_INIT>
+      : mode == ACC_ADD  ? k_grad_accum_multi<false, ACC_ADD> : k_grad_accum_multi<false, ACC_FOLD>;
+  hipLaunchKernelGGL(k, dim3(nblocks), dim3(256), 0, s, ts, block_start, ntensors);
   return (int)hipGetLastError();
 }
 

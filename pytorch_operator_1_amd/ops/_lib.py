@@ -132,6 +132,9 @@ _SIGS = {
     "pto_grad_norm_finalize": [_P, _I, _F, _F, _P, _P],
     "pto_adamw_multi_clip": [_P, _P, _I, _I, _I, _P, _F, _F, _F, _F, _F, _I, _F, _P, _I, _P],
     "pto_sgd_multi_clip": [_P, _P, _I, _I, _P, _F, _F, _F, _F, _P, _I, _I, _P, _L, _P],
+    # fp32 micro-batch gradient accumulation (optim_kernels.hip)
+    "pto_grad_accum_block_count": [_L],
+    "pto_grad_accum_multi": [_P, _P, _I, _I, _I, _I, _P],
     # LLM memory-bound kernels (csrc/kernels/llm_kernels.hip)
     "pto_add_rmsnorm_fwd": [_P, _P, _P, _P, _P, _P, _L, _I, _F, _P],
     "pto_rmsnorm_bwd_groups": [_L],

@@ -120,6 +120,79 @@ def _upload(host: torch.Tensor, device) -> torch.Tensor:
     return host.pin_memory().to(device, non_blocking=True)
 
 
+class _AccumTensor(ctypes.Structure):
+    _fields_ = [("g", ctypes.c_void_p), ("acc", ctypes.c_void_p), ("out", ctypes.c_void_p), ("n", ctypes.c_longlong)]
+
+
+ACCUM_MODES = {"init": 0, "add": 1, "fold": 2}
+
+
+@torch.no_grad()
+def grad_accum_multi(records, mode: str) -> None:
+    """Micro-batch gradient accumulation in fp32, one HIP launch per
+    gradient dtype (``k_grad_accum_multi``, csrc/kernels/optim_kernels.hip).
+
+    ``records``: ``(grad or None, acc, out or None)`` per parameter; ``acc``
+    is fp32, ``grad`` and ``out`` bf16 or fp32 in ``acc``'s dense layout.
+
+    * ``"init"``: ``acc = float(grad)``  (first micro-batch: no zeroing pass)
+    * ``"add"``:  ``acc += float(grad)``  (one fp32 add)
+    * ``"fold"``: ``out = (acc + float(grad)).to(out.dtype)``, ``acc`` is left
+      as it is; ``out`` may be ``grad`` itself.
+
+    ``grad=None`` is a parameter that received no gradient in this
+    micro-batch and counts as zero: zeros / nothing / ``out = acc.to(dtype)``.
+    CPU tensors take the same arithmetic through torch ops."""
+    if mode not in ACCUM_MODES:
+        raise ValueError(f"grad_accum_multi: mode must be one of {sorted(ACCUM_MODES)}, not {mode!r}")
+    fold = mode == "fold"
+    by_dtype: dict = {}
+    for g, acc, out in records:
+        if acc.dtype != torch.float32 or not _same_dense_layout(acc, g, out):
+            raise ValueError("grad_accum_multi: fp32 accumulators with grads/outputs of the same dense layout required")
+        if fold != (out is not None):
+            raise ValueError("grad_accum_multi: an output is given for 'fold' and only for it")
+        src = g if g is not None else out  # neither: 'init'/'add' of a missing gradient, any instance does
+        if src is not None and (src.dtype not in (torch.float32, torch.bfloat16) or
+                                (fold and g is not None and g.dtype != out.dtype)):
+            raise ValueError("grad_accum_multi: gradients and outputs must be bf16 or fp32, and of one dtype")
+        by_dtype.setdefault(None if src is None else src.dtype, []).append((g, acc, out))
+    loose = by_dtype.pop(None, [])
+    if loose:
+        by_dtype.setdefault(next(iter(by_dtype), torch.float32), []).extend(loose)
+    for dt, recs in by_dtype.items():
+        if recs[0][1].device.type != "cuda":
+            for g, acc, out in recs:
+                if mode == "init":
+                    if g is None:
+                        acc.zero_()
+                    else:
+                        acc.copy_(g)
+                elif mode == "add":
+                    if g is not None:
+                        acc.add_(g.float())
+                else:
+                    out.copy_((acc if g is None else acc + g.float()).to(out.dtype))
+            continue
+        L = _lib.lib()
+        raw = (_AccumTensor * len(recs))()
+        starts, nb = [], 0
+        for r, (g, acc, out) in zip(raw, recs):
+            r.g, r.acc, r.out, r.n = _lib.ptr(g), acc.data_ptr(), _lib.ptr(out), acc.numel()
+            starts.append(nb)
+            nb += L.pto_grad_accum_block_count(acc.numel())
+        # records and block prefix in ONE upload (a launch per bucket per micro-batch)
+        nrec = ctypes.sizeof(raw)
+        host = torch.empty(nrec + 4 * len(recs), dtype=torch.uint8)
+        ctypes.memmove(host.data_ptr(), ctypes.addressof(raw), nrec)
+        host[nrec:].view(torch.int32).copy_(torch.tensor(starts, dtype=torch.int32))
+        dev = recs[0][1].device
+        table = _upload(host, dev)  # freed after the launch below, in stream order
+        _lib.check(L.pto_grad_accum_multi(table.data_ptr(), table.data_ptr() + nrec, len(recs), nb,
+                                          int(dt == torch.bfloat16), ACCUM_MODES[mode], _lib.stream_ptr(dev)),
+                   "grad_accum_multi")
+
+
 def _to_device(host: torch.Tensor, device, pending: list | None, reserved: list | None = None):
     """``host.to(device)``; while a HIP graph is being captured the copy is
     deferred (``pending``, see :meth:`FusedSGD.finish_capture`): the launch

@@ -78,10 +78,23 @@ class GradBucketer:
     * ``none`` — single process: no buckets, gradients stay the tensors
       autograd produced (zero extra passes).
     After the optimizer step call :meth:`release` (``copy``/``none``).
+
+    ``accum_steps=N > 1`` (``copy``/``none``): one optimizer step over N
+    micro-batches.  :meth:`finish` is called after every backward; the first
+    N-1 calls sum the fresh gradients into fp32 accumulators (one per
+    parameter, the parameter's layout) with
+    :func:`..ops.optim.grad_accum_multi`, issue no collective, wait on
+    nothing and leave every ``param.grad`` ``None``.  The N-th
+    (:attr:`at_boundary`) folds accumulators plus fresh gradients, rounded
+    once to the gradient dtype, into what it would otherwise have copied (the
+    bucket slots, or autograd's tensors in place), and the all-reduce runs as
+    with N = 1.  The first micro-batch overwrites the accumulators, so they
+    are never zeroed and are dead between optimizer steps.
     """
 
     def __init__(self, module: torch.nn.Module, bucket_mb: float | None = None, process_group=None,
-                 overlap: bool = True, mode: str | None = None, comm: str | None = None, force_ddp: bool = False):
+                 overlap: bool = True, mode: str | None = None, comm: str | None = None, force_ddp: bool = False,
+                 accum_steps: int = 1):
         """``comm``: "auto" (default, ``PTO_COMM``): per-bucket xGMI kernel
         vs RCCL by measurement; "xgmi": every bucket on the kernel; "rccl":
         never the kernel.  ``force_ddp``: the multi-rank machinery (flat
@@ -98,6 +111,12 @@ class GradBucketer:
         self.mode = mode or os.environ.get("PTO_GRAD_MODE") or ("copy" if self.ddp else "none")
         if self.mode not in ("view", "copy", "none"):
             raise ValueError(f"GradBucketer: unknown mode {self.mode}")
+        self.accum_steps = int(accum_steps)
+        if self.accum_steps < 1:
+            raise ValueError(f"GradBucketer: accum_steps must be >= 1, got {accum_steps}")
+        if self.accum_steps > 1 and self.mode == "view":
+            raise ValueError("GradBucketer: accum_steps > 1 is not supported in mode 'view' (autograd already adds "
+                             "into the flat buffer there, in the gradient's dtype); use mode 'copy'")
         params = [p for p in module.parameters() if p.requires_grad]
         if not params:
             raise ValueError("GradBucketer: module has no trainable parameters")
@@ -137,6 +156,9 @@ class GradBucketer:
                 if (end - start) * buf.element_size() >= cap or j + 1 == len(ps):
                     self.buckets.append(dict(params=cur, dtype=dt, lo=start, hi=end))
                     cur, start = [], end
+        # fp32 running sums of the micro-batch gradients (accum_steps > 1 only)
+        self._acc = {p: torch.empty_like(p, dtype=torch.float32) for p in params} if self.accum_steps > 1 else {}
+        self._micro = 0  # finish() calls modulo accum_steps
         self._bucket_of = {}
         for i, b in enumerate(self.buckets):
             for p in b["params"]:
@@ -234,28 +256,86 @@ class GradBucketer:
         i = self._bucket_of[p]
         if self.mode == "copy":
             v = self._views[p]
-            if p.grad is not v:  # copied with the rest of its bucket, one multi-tensor launch
+            if self.accum_steps > 1:
+                # summed (at the boundary: folded into its slot) with the rest of its
+                # bucket; until that launch the list keeps the fresh gradient alive
+                self._copies[i].append((p, p.grad))
+                p.grad = v if self.at_boundary else None
+            elif p.grad is not v:  # copied with the rest of its bucket, one multi-tensor launch
                 self._copies[i].append((v, p.grad))
                 p.grad = v
         self._pending[i] -= 1
         if self._pending[i] == 0:
             self._flush(i)
-            if self.overlap:
+            if self.overlap and self.at_boundary:
                 self._launch(i)
 
     def _flush(self, i):
         """Copy bucket ``i``'s gradients into their slots: ONE multi-tensor
         launch per bucket instead of one copy kernel per parameter (161 on
-        ResNet-50: ~0.8 ms/step of launch-bound copies)."""
+        ResNet-50: ~0.8 ms/step of launch-bound copies).  With
+        ``accum_steps > 1`` that launch is the accumulation: INIT / ADD into
+        the fp32 sums, at the boundary FOLD into the slots (the same bytes
+        written as by the copy)."""
         cp = self._copies[i]
-        if cp:
+        if cp and self.accum_steps > 1:
+            self._accumulate([(g, self._acc[p], self._views[p] if self.at_boundary else None) for p, g in cp])
+            self._copies[i] = []
+        elif cp:
             torch._foreach_copy_([v for v, _ in cp], [g for _, g in cp])
             self._copies[i] = []
 
+    @property
+    def at_boundary(self) -> bool:
+        """True while the micro-batch in flight is the last of its optimizer
+        step: its :meth:`finish` all-reduces and the optimizer follows
+        (always, with ``accum_steps == 1``)."""
+        return self._micro == self.accum_steps - 1
+
+    def _accumulate(self, records):
+        from ..ops.optim import grad_accum_multi
+
+        grad_accum_multi(records, "fold" if self.at_boundary else ("init" if self._micro == 0 else "add"))
+
+    def _finish_micro(self):
+        """``accum_steps > 1``: what :meth:`finish` does with this
+        micro-batch's gradients before any collective."""
+        boundary = self.at_boundary
+        if self.mode == "copy":
+            for i, b in enumerate(self.buckets):
+                if self._pending[i] > 0:  # some of its params got no gradient: null records
+                    have = {id(p) for p, _ in self._copies[i]}
+                    for p in b["params"]:
+                        if id(p) not in have:
+                            self._copies[i].append((p, None))
+                            if boundary:
+                                p.grad = self._views[p]
+                    self._flush(i)
+            return
+        # "none": one launch per gradient dtype over all parameters; the boundary folds in place
+        records = []
+        for p in self.params:
+            g = p.grad
+            if boundary and g is None:
+                p.grad = torch.empty_like(p)
+            records.append((g, self._acc[p], p.grad if boundary else None))
+            if not boundary:
+                p.grad = None
+        self._accumulate(records)
+
     def finish(self):
         """Call after ``loss.backward()``: launches any bucket whose params
-        produced no gradient, waits for all collectives, joins the streams."""
-        if self.mode == "copy":
+        produced no gradient, waits for all collectives, joins the streams.
+        With ``accum_steps > 1`` only every ``accum_steps``-th call does so;
+        the others sum the gradients and return."""
+        if self.accum_steps > 1:
+            self._finish_micro()
+            if not self.at_boundary:
+                self._micro += 1
+                self.reset()
+                return
+            self._micro = 0
+        elif self.mode == "copy":
             for p, v in self._views.items():  # params that got no gradient this step
                 if p.grad is not v:
                     if p.grad is None:
@@ -296,8 +376,9 @@ class GradBucketer:
 
     @property
     def grad_scale(self) -> float:
-        """Factor the optimizer folds into its gradient read (SUM -> mean)."""
-        return 1.0 / self.world
+        """Factor the optimizer folds into its gradient read (SUM -> mean
+        over the ranks and their micro-batches)."""
+        return 1.0 / (self.world * self.accum_steps)
 
     def zero_(self):
         for buf in self.flat.values():
@@ -313,3 +394,7 @@ class GradBucketer:
 
     def grad_bytes(self) -> int:
         return sum(b.numel() * b.element_size() for b in self.flat.values())
+
+    def accum_bytes(self) -> int:
+        """Bytes of the fp32 micro-batch accumulators (0 with ``accum_steps == 1``)."""
+        return sum(a.numel() * a.element_size() for a in self._acc.values())

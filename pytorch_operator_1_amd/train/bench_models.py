@@ -60,6 +60,19 @@ def _scalar(t):
     return None if t is None else float(t)
 
 
+def _accum_steps(n) -> int:
+    if int(n) != n or n < 1:
+        raise ValueError(f"grad_accum_steps must be an integer >= 1, got {n}")
+    return int(n)
+
+
+def _accum_text(n: int, bucketer) -> str:
+    if n == 1:
+        return "off"
+    return (f"{n} micro-batches per optimizer step, fp32 sums on the device "
+            f"({bucketer.accum_bytes() / 2**20:.0f} MB of accumulators)")
+
+
 def _clip_text(max_grad_norm):
     if max_grad_norm is None:
         return "off"
@@ -72,7 +85,12 @@ class CheckpointMixin:
     """Named tensors of the full training state (parameters, buffers,
     optimizer state) for :class:`..train.checkpoint.ShardedCheckpointer`,
     and the inverse.  DDP replicas hold identical copies, so the sharded
-    checkpointer writes each tensor once (its owner rank)."""
+    checkpointer writes each tensor once (its owner rank).
+
+    Checkpoints are taken between optimizer steps.  There the bucketer's
+    fp32 micro-batch accumulators (``grad_accum_steps > 1``) are dead: the
+    first micro-batch of the next step overwrites them.  So they are not
+    checkpointed, and a run resumes the same with any ``grad_accum_steps``."""
 
     def _param_names(self):
         return {p: n for n, p in self.model.named_parameters()}
@@ -126,15 +144,25 @@ class ResNetTrainer(CheckpointMixin):
     (``GradBucketer`` mode ``none``).  Off by default: at batch 256 the GPU
     is never starved by the ~1,400 eager launches per step (26.74 vs 26.73
     ms/step measured, profiles/resnet50_r5.md), so the graph buys nothing
-    here -- it is for smaller per-GPU batches, where launch latency shows."""
+    here -- it is for smaller per-GPU batches, where launch latency shows.
+
+    ``grad_accum_steps=N``: one optimizer step over N micro-batches of
+    ``batch_size`` (see :class:`LlamaTrainer`); not with the captured step."""
 
     EAGER_STEPS = 2
 
     def __init__(self, device, batch_size: int = 256, image_size: int = 224, lr: float = 0.1,
                  momentum: float = 0.9, weight_decay: float = 1e-4, seed: int = 0, bucket_mb: float | None = None,
-                 force_ddp: bool = False, graph: bool | None = None, max_grad_norm: float | None = None):
+                 force_ddp: bool = False, graph: bool | None = None, max_grad_norm: float | None = None,
+                 grad_accum_steps: int = 1):
         from ..models.resnet import resnet50, synthetic_images
 
+        self.grad_accum_steps = _accum_steps(grad_accum_steps)
+        if graph is None:
+            graph = os.environ.get("PTO_STEP_GRAPH", "0") == "1"
+        if graph and self.grad_accum_steps > 1:
+            raise ValueError("ResNetTrainer: the captured step (graph=True / PTO_STEP_GRAPH=1) is one micro-batch "
+                             "per optimizer step; use grad_accum_steps=1 or graph=False")
         torch.manual_seed(seed)
         # MIOpen find: benchmark the conv solvers once per shape (warmup) and
         # keep the fastest instead of the heuristic pick
@@ -144,7 +172,8 @@ class ResNetTrainer(CheckpointMixin):
         self.max_grad_norm = max_grad_norm  # global-norm clip (inf: report only); fixed once a step is captured
         self.model = resnet50().to(device=device, memory_format=torch.channels_last)
         self.model.train()
-        self.bucketer = GradBucketer(self.model, bucket_mb=bucket_mb, force_ddp=force_ddp)
+        self.bucketer = GradBucketer(self.model, bucket_mb=bucket_mb, force_ddp=force_ddp,
+                                     accum_steps=self.grad_accum_steps)
         if device.type == "cuda":
             self.opt = FusedSGD(self.model.parameters(), lr=lr, momentum=momentum, weight_decay=weight_decay)
         else:
@@ -152,13 +181,13 @@ class ResNetTrainer(CheckpointMixin):
                                                  weight_decay=weight_decay))
         # images arrive in the compute dtype on the GPU (what a GPU-side
         # decode/normalise stage hands over); the model casts nothing per step
-        self.x, self.y = synthetic_images(batch_size, device, image_size, seed=seed,
+        self.x, self.y = synthetic_images(batch_size * self.grad_accum_steps, device, image_size, seed=seed,
                                           dtype=torch.bfloat16 if device.type == "cuda" else torch.float32)
+        # the fixed micro-batches of one optimizer step: the rows of ONE batch of batch_size * N
+        self._micro = list(zip(self.x.split(batch_size), self.y.split(batch_size)))
         self._loss = None
         self.steps_done = 0
         self.timer = StepTimer(device, enabled=False)
-        if graph is None:
-            graph = os.environ.get("PTO_STEP_GRAPH", "0") == "1"
         self.use_graph = bool(graph) and device.type == "cuda" and self.bucketer.mode == "none"
         self._graph = None
         self._eager_done = 0
@@ -196,15 +225,20 @@ class ResNetTrainer(CheckpointMixin):
 
     def _eager_step(self):
         t = self.timer
-        with t.phase("forward"), torch.autocast(device_type=self.device.type, dtype=torch.bfloat16):
-            out = self.model(self.x)
-        with t.phase("forward"):
-            loss = F.cross_entropy(out.float(), self.y)
-        with t.phase("backward"):
-            loss.backward()
-            GradStash.assert_drained()  # host counter: no sibling conv1x1 gradient left parked
-        with t.phase("allreduce_wait"):
-            self.bucketer.finish()
+        total = None
+        for x, y in self._micro:
+            with t.phase("forward"), torch.autocast(device_type=self.device.type, dtype=torch.bfloat16):
+                out = self.model(x)
+            with t.phase("forward"):
+                loss = F.cross_entropy(out.float(), y)
+            with t.phase("backward"):
+                loss.backward()
+                GradStash.assert_drained()  # host counter: no sibling conv1x1 gradient left parked
+            with t.phase("allreduce_wait"):  # not the last micro-batch: the fp32 accumulation, no collective
+                self.bucketer.finish()
+            total = loss.detach() if total is None else total + loss.detach()
+        if self.grad_accum_steps > 1:
+            loss = total / self.grad_accum_steps
         with t.phase("optimizer"):
             self.opt.step(grad_scale=self.bucketer.grad_scale, zero_grad=self.bucketer.optimizer_zeroes_grads,
                           max_grad_norm=self.max_grad_norm)
@@ -226,23 +260,35 @@ class ResNetTrainer(CheckpointMixin):
         return _scalar(self.opt.clip_coef) if self.max_grad_norm is not None else None
 
     def samples_per_step(self) -> int:
-        return self.batch_size
+        return self.batch_size * self.grad_accum_steps
 
     def describe(self) -> dict:
         return {"model": "resnet50 (v1.5, 25.6M params)", "input_shape": [3, 224, 224],
                 "optimizer": "SGD momentum=0.9 wd=1e-4 (FusedSGD HIP)", "amp": "bf16 autocast, fp32 master",
                 "step": (f"whole step replayed as one HIP graph (after {self.EAGER_STEPS} eager steps)"
                          if self.use_graph else "eager"),
-                "grad_clip": _clip_text(self.max_grad_norm)}
+                "grad_clip": _clip_text(self.max_grad_norm),
+                "grad_accum": _accum_text(self.grad_accum_steps, self.bucketer)}
 
 
 class LlamaTrainer(CheckpointMixin):
     def __init__(self, device, model: str = "llama3-8b", batch_size: int = 2, seq_len: int = 4096,
                  lr: float = 3e-4, weight_decay: float = 0.1, seed: int = 0, checkpoint: str = "none",
                  impl: str | None = None, bucket_mb: float | None = None, force_ddp: bool = False,
-                 max_grad_norm: float | None = None):
+                 max_grad_norm: float | None = None, grad_accum_steps: int = 1):
+        """``grad_accum_steps=N``: :meth:`step` stays ONE optimizer step and
+        runs N micro-batches of ``batch_size`` rows (forward, backward,
+        ``bucketer.finish()``), summing their gradients in fp32 on the device
+        (:class:`..parallel.ddp.GradBucketer`); optimizer, weight
+        re-transposes and all-reduce are paid once per N.  The synthetic data
+        is ONE batch of ``batch_size * N`` rows cut into N fixed micro-batches.
+        Every micro-batch loss is a mean over its own tokens and the step
+        weighs them 1/N each, which is the mean over all tokens only when the
+        micro-batches hold equally many valid tokens (true of the synthetic
+        data; a loader with padding would have to weigh by token count)."""
         from ..models.llama import CONFIGS, Llama, synthetic_tokens
 
+        self.grad_accum_steps = _accum_steps(grad_accum_steps)
         torch.manual_seed(seed)
         impl = impl or ("hip" if device.type == "cuda" else "torch")
         self.cfg = CONFIGS[model]
@@ -257,26 +303,34 @@ class LlamaTrainer(CheckpointMixin):
         self.transposed_dgrad = impl == "hip" and os.environ.get("PTO_WT", "1") == "1"
         if self.transposed_dgrad:
             self.model.enable_transposed_dgrad()
-        self.bucketer = GradBucketer(self.model, bucket_mb=bucket_mb, force_ddp=force_ddp)
+        self.bucketer = GradBucketer(self.model, bucket_mb=bucket_mb, force_ddp=force_ddp,
+                                     accum_steps=self.grad_accum_steps)
         if device.type == "cuda":
             self.opt = FusedAdamW(self.model.parameters(), lr=lr, betas=(0.9, 0.95), eps=1e-8,
                                   weight_decay=weight_decay)
         else:  # CPU: stock AdamW on the bf16 params (tests of the checkpoint/resume path)
             self.opt = _TorchOpt(torch.optim.AdamW(self.model.parameters(), lr=lr, betas=(0.9, 0.95), eps=1e-8,
                                                    weight_decay=weight_decay))
-        self.tokens, self.labels = synthetic_tokens(batch_size, seq_len, self.cfg.vocab_size, device, seed=seed)
+        self.tokens, self.labels = synthetic_tokens(batch_size * self.grad_accum_steps, seq_len, self.cfg.vocab_size,
+                                                    device, seed=seed)
+        self._micro = list(zip(self.tokens.split(batch_size), self.labels.split(batch_size)))
         self._loss = None
         self.steps_done = 0
         self.timer = StepTimer(device, enabled=False)
 
     def step(self):
         t = self.timer
-        with t.phase("forward"):
-            loss = self.model(self.tokens, self.labels)
-        with t.phase("backward"):
-            loss.backward()
-        with t.phase("allreduce_wait"):
-            self.bucketer.finish()
+        total = None
+        for tokens, labels in self._micro:
+            with t.phase("forward"):
+                loss = self.model(tokens, labels)
+            with t.phase("backward"):
+                loss.backward()
+            with t.phase("allreduce_wait"):  # not the last micro-batch: the fp32 accumulation, no collective
+                self.bucketer.finish()
+            total = loss.detach() if total is None else total + loss.detach()
+        if self.grad_accum_steps > 1:
+            loss = total / self.grad_accum_steps  # on the device, no sync
         with t.phase("optimizer"):
             self.opt.step(grad_scale=self.bucketer.grad_scale, zero_grad=self.bucketer.optimizer_zeroes_grads,
                           max_grad_norm=self.max_grad_norm)
@@ -300,7 +354,7 @@ class LlamaTrainer(CheckpointMixin):
         return _scalar(self.opt.clip_coef) if self.max_grad_norm is not None else None
 
     def samples_per_step(self) -> int:
-        return self.batch_size * self.seq_len  # tokens
+        return self.batch_size * self.grad_accum_steps * self.seq_len  # tokens
 
     def flops_per_step(self) -> float:
         return self.cfg.train_flops_per_token(self.seq_len) * self.samples_per_step()
@@ -311,4 +365,5 @@ class LlamaTrainer(CheckpointMixin):
                 "amp": "bf16 params/activations, fp32 optimizer state",
                 "checkpoint": self.model.checkpoint,
                 "dgrad": "W^T copies (K-contiguous dX GEMMs)" if self.transposed_dgrad else "F.linear",
-                "grad_clip": _clip_text(self.max_grad_norm)}
+                "grad_clip": _clip_text(self.max_grad_norm),
+                "grad_accum": _accum_text(self.grad_accum_steps, self.bucketer)}

@@ -14,6 +14,9 @@ but a restarted replica starts from step 0.  Here:
   thread, the manifest committed last;
 * on start the newest committed step is restored (own shard read, owners
   broadcast) and training continues from it ("Resumed from <dir> at step N");
+* ``--grad-accum-steps N`` makes every step N micro-batches of
+  ``--batch-size`` with one optimizer update (fp32 gradient sums on the
+  device); checkpoints fall between optimizer steps and need nothing extra;
 * a collective failure exits 138 (retryable for ``restartPolicy: ExitCode``)
   exactly like the MNIST trainer, so kill/rejoin works for these models too.
 
@@ -60,7 +63,12 @@ def parse_args(argv=None):
     p.add_argument("--max-grad-norm", type=float, default=None,
                    help="clip the global gradient norm to this value on the device and log it "
                         "(inf: log the norm without clipping; default: off)")
+    p.add_argument("--grad-accum-steps", type=int, default=1,
+                   help="micro-batches of --batch-size per optimizer step, their gradients summed in fp32 on "
+                        "the device (default 1: off); --steps counts optimizer steps")
     args = p.parse_args(argv)
+    if args.grad_accum_steps < 1:
+        p.error("--grad-accum-steps must be >= 1")
     if args.max_grad_norm is not None and not args.max_grad_norm >= 0:
         p.error("--max-grad-norm must be >= 0")
     return args
@@ -72,11 +80,11 @@ def build(args, device):
     if args.model == "resnet50":
         kw = {} if args.lr is None else {"lr": args.lr}
         return ResNetTrainer(device, batch_size=args.batch_size or 64, image_size=args.image_size, seed=args.seed,
-                             max_grad_norm=args.max_grad_norm, **kw)
+                             max_grad_norm=args.max_grad_norm, grad_accum_steps=args.grad_accum_steps, **kw)
     kw = {} if args.lr is None else {"lr": args.lr}
     return LlamaTrainer(device, model=args.model, batch_size=args.batch_size or 2, seq_len=args.seq_len,
                         seed=args.seed, checkpoint=args.activation_checkpoint, max_grad_norm=args.max_grad_norm,
-                        **kw)
+                        grad_accum_steps=args.grad_accum_steps, **kw)
 
 
 def _main(argv=None):

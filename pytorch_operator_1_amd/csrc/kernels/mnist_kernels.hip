@@ -289,9 +289,12 @@ __global__ __launch_bounds__(256) void k_conv2_fwd(const float* __restrict__ a1p
 // -------------------------------------------------------------- F1+F2 ----
 // conv1 and conv2 forward in ONE launch.  Block = (sample, 16-channel conv2
 // tile), 1024 threads; each block recomputes the sample's whole pooled conv1
-// map straight into LDS (2880 outputs x 100 FMAs: cheaper than a kernel
-// boundary) and the nt == 0 block also writes it (+ argmax codes) to HBM for
-// the backward pass.
+// map (+ argmax codes) straight into LDS (2880 outputs x 100 FMAs: cheaper
+// than a kernel boundary); after the barrier that closes conv1 each of the
+// sample's four blocks writes one quarter of the map, of the codes and of
+// the image to HBM for the backward pass, as 16-byte write-through stores
+// from LDS (the nt == 0 block used to issue them all, a dword and a byte
+// store per output inside the FMA loop).
 //  * conv1: a lane task is (channel pair, pooled pixel): 100 packed FMAs
 //    (v_pk_fma_f32, the pair's weights interleaved in LDS), the 6x6 input
 //    patch read as float2 pairs.  20 full wave tasks (pair x 64-pixel chunk,
@@ -301,7 +304,14 @@ __global__ __launch_bounds__(256) void k_conv2_fwd(const float* __restrict__ a1p
 //    wave sets (7+6+6+6 groups of 5 MFMAs), partial tiles combined through
 //    LDS, so each SIMD interleaves independent MFMA chains.
 //  * lazy conv1 update (one-process schedule, LazyConv1), the image copy
-//    for the backward (xout) and the conv2.weight snapshot (w2out).
+//    for the backward (xout) and the conv2.weight snapshot (w2out, written
+//    through as well).  a2p / code2 leave as plain stores in the block's last
+//    instructions: staged into 16-byte rows they measured slower, written
+//    through or not (profiles/f12_conv1_chain.md).
+//  * the conv1 phase (2.4 us) does not move with the register budget (128
+//    VGPRs, a task's reads issued ahead of its chain), with round 1's patch
+//    prefetched under round 0's chain, or with cheaper patch reads: all
+//    measured, none kept (same profile).
 //  * ARM != 0 (overlapped multi-GPU step, fused_step.py "ddp-xgmi"): the
 //    PREVIOUS step's gradient exchange runs as two roles ahead of the conv
 //    blocks in the grid (protocol ARM-1):
@@ -371,6 +381,21 @@ PTO_DEV void wait_conv_role(const ArRole& cv) {
   }
 }
 constexpr int W1PLD = 52;  // a channel pair's 25 interleaved taps, padded to whole float4
+
+// 16-byte store at byte offset `off` of [base, base + bytes) that writes
+// through the L2 (sc1).  F12 hands a1p, code1, the image copy and the
+// conv2.weight snapshot (1.2 MB at batch 64) to the backward; left dirty in
+// the L2s they are written back at the launch boundary, on the next launch's
+// time (plain stores: step 33.1 us, write-through: 32.7 us,
+// profiles/f12_conv1_chain.md).  A buffer store: an offset past `bytes` is
+// dropped by the hardware's range check.
+PTO_DEV void st16_wt(void* base, int bytes, int off, float4 v) {
+  constexpr int AUX_SC1 = 16;
+  __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(pto_ar::v4u, v),
+                                         __builtin_amdgcn_make_buffer_rsrc(base, 0, bytes, 0x00020000), off, 0,
+                                         AUX_SC1);
+}
+
 template <int NTH, int ARM = 0>
 __global__ __launch_bounds__(NTH, ARM ? 2 * NTH / 256 : 1) void k_conv12_fwd2_t(
     const float* __restrict__ x, const float* __restrict__ w1, const float* __restrict__ b1,
@@ -398,6 +423,7 @@ __global__ __launch_bounds__(NTH, ARM ? 2 * NTH / 256 : 1) void k_conv12_fwd2_t(
   constexpr bool SYS = ARM != 0;  // conv parameters written by this launch's conv role
   __shared__ float ws[16 * WS_LD];
   __shared__ __attribute__((aligned(16))) float in_s[A1P];
+  __shared__ __attribute__((aligned(16))) uint8_t code_s[A1P];  // conv1's argmax codes, next to in_s
   __shared__ __attribute__((aligned(16))) float xs[784];
   __shared__ float b1s[C1];
   // the full tasks' channel pairs interleaved, (w[2p][k], w[2p+1][k]) per
@@ -461,16 +487,11 @@ __global__ __launch_bounds__(NTH, ARM ? 2 * NTH / 256 : 1) void k_conv12_fwd2_t(
         d[0] = wv[q].x; d[1] = wv[q].y; d[2] = wv[q].z; d[3] = wv[q].w;
       }
     }
-    if (tid < 196) {
-      reinterpret_cast<float4*>(xs)[tid] = xv;
-      if (lz.xout && nt == 0) reinterpret_cast<float4*>(lz.xout + b * 784)[tid] = xv;
-    }
+    if (tid < 196) reinterpret_cast<float4*>(xs)[tid] = xv;
     if (lz.w2out && b == 0) {  // conv2.weight snapshot: rows nt*16.. (one writer per row)
 #pragma unroll
-      for (int q = 0; q < 2048 / NTH; ++q) {
-        const int e = tid + NTH * q;
-        if (e < nrows * 125) reinterpret_cast<float4*>(lz.w2out + nt * 16 * 500)[e] = wv[q];
-      }
+      for (int q = 0; q < 2048 / NTH; ++q)
+        st16_wt(lz.w2out + nt * 16 * 500, nrows * 2000, (tid + NTH * q) * 16, wv[q]);
     }
 #pragma unroll
     for (int q = 0; q < QW1; ++q) {
@@ -559,14 +580,27 @@ __global__ __launch_bounds__(NTH, ARM ? 2 * NTH / 256 : 1) void k_conv12_fwd2_t(
       uint8_t cd;
       relu_pool4(v, o, cd);
       in_s[oc * 144 + pix] = o;
-      if (nt == 0) {
-        a1p[b * A1P + oc * 144 + pix] = o;
-        code1[b * A1P + oc * 144 + pix] = cd;
-      }
+      code_s[oc * 144 + pix] = cd;
     }
   }
   __syncthreads();
   PTO_STAMP(2);
+  {
+    // The copies for the backward, straight from LDS as 16-byte write-through
+    // stores: each of the sample's four nt workgroups stores its quarter of
+    // a1p (180 float4), of code1 (45 rows of 16 codes) and of the image (49
+    // float4), on waves of the shorter conv2 K parts.  One writer per byte.
+    static_assert(A1P % 64 == 0 && 784 % 16 == 0, "quarters of whole 16-byte rows");
+    constexpr int QA = A1P / 16, QC = A1P / 64, QX = 784 / 16;
+    const int ua = tid - 256, uc = tid - 512, ux = tid - 768;
+    const float4* in4 = reinterpret_cast<const float4*>(in_s);
+    const float4* code4 = reinterpret_cast<const float4*>(code_s);
+    const float4* x4 = reinterpret_cast<const float4*>(xs);
+    if (ua >= 0 && ua < QA) st16_wt(a1p + (size_t)b * A1P, A1P * 4, (nt * QA + ua) * 16, in4[nt * QA + ua]);
+    if (uc >= 0 && uc < QC) st16_wt(code1 + (size_t)b * A1P, A1P, (nt * QC + uc) * 16, code4[nt * QC + uc]);
+    if (lz.xout && ux >= 0 && ux < QX)
+      st16_wt(lz.xout + (size_t)b * 784, 784 * 4, (nt * QX + ux) * 16, x4[nt * QX + ux]);
+  }
   // conv2 implicit GEMM (k_conv2_fwd's lane maps), K (25 groups of 5 MFMAs)
   // split over NPART wave sets: 13+12 (512 threads) or 7+6+6+6 (1024)
   const int t = wid & 3, half = wid >> 2;
@@ -2383,6 +2417,11 @@ static SgdArgs sgd_args(const float* lr, float mom, float wd, float gscale, int 
   return a;
 }
 
+// F12 stores its copies for the backward 16 bytes at a time (null: not written)
+static bool f12_copies_aligned(const void* a1p, const void* code1, const void* xout, const void* w2out) {
+  return ((((uintptr_t)a1p) | ((uintptr_t)code1) | ((uintptr_t)xout) | ((uintptr_t)w2out)) & 15) == 0;
+}
+
 // F12: conv1 + conv2 forward.  g1f/m1f/pending non-null: conv1's owed SGD
 // update is applied on the fly (flat conv1 grads/momentum, weights at 0,
 // bias at bias_off, `nrep` gradient replicas at rep + r*rep_stride); xout:
@@ -2395,6 +2434,7 @@ PTO_API int pto_conv12_fwd_lazy_x(const float* x, const float* w1, const float* 
                                   float* xout, float* w2out, const float* rep, int nrep, int rep_stride,
                                   hipStream_t s) {
   if (nrep < 1 || nrep > C1_MAXREP || (nrep > 1 && !rep) || (pending && (!g1f || !m1f || !lr))) return -1;
+  if (!f12_copies_aligned(a1p, code1, xout, w2out)) return -1;
   LazyConv1 lz{g1f, m1f, pending, sgd_args(lr, mom, wd, gscale, nesterov), bias_off, xout, w2out, rep, nrep,
                rep_stride};
   hipLaunchKernelGGL(HIP_KERNEL_NAME(k_conv12_fwd2_t<1024, 0>), dim3(B * 4), dim3(1024), 0, s, x, w1, b1, w2, b2, a1p,
@@ -2434,6 +2474,7 @@ PTO_API int pto_conv12_fwd_ar(const float* x, const float* w1, const float* b1, 
                                                       rep_base < cv_off + cv_n || rep_from < cv_off ||
                                                       rep_from + rep_stride > cv_off + cv_n)))
     return -1;
+  if (!f12_copies_aligned(a1p, code1, xout, nullptr)) return -1;
   LazyConv1 lz{nullptr, nullptr, nullptr, sgd_args(lr, mom, wd, gscale, nesterov), 0, xout, nullptr, nullptr, 1, 0};
   ArRole ar{}, cv{};
   for (ArRole* r : {&ar, &cv}) {

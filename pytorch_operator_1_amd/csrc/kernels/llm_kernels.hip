@@ -446,13 +446,17 @@ __global__ __launch_bounds__(NT) void k_rope(const uint16_t* src, uint16_t* dst,
 
 // ---------------------------------------------------------------- cross entropy
 // One block per row of V logits (bf16).  fwd: lse[m], loss[m] (0 for ignored).
+// EXT adds label smoothing eps and the z-loss zc * lse^2 to the row loss,
+//   loss[m] = (1-eps)*(lse - z[y]) + eps*(lse - mean(z)) + zc*lse^2,
+// from one more running sum over the same loads; EXT=false is plain NLL.
+template <bool EXT>
 __global__ __launch_bounds__(NT) void k_ce_fwd(const uint16_t* __restrict__ logits, const long long* __restrict__ labels,
                                                float* __restrict__ lse, float* __restrict__ loss, int V,
-                                               long long ignore_index) {
+                                               long long ignore_index, float eps, float zc) {
   __shared__ float red[4];
   const long long row = blockIdx.x;
   const uint16_t* z = logits + row * V;
-  float mx = -INFINITY, sum = 0.f;
+  float mx = -INFINITY, sum = 0.f, zs = 0.f;
   const int V8n = V >> 3;
   for (int i = threadIdx.x; i < V8n; i += NT) {  // online max/sum, 8 logits at a time
     const V8 a = ld8(z + i * 8);
@@ -465,6 +469,10 @@ __global__ __launch_bounds__(NT) void k_ce_fwd(const uint16_t* __restrict__ logi
     }
 #pragma unroll
     for (int e = 0; e < 8; ++e) sum += __expf(a.v[e] - mx);
+    if (EXT) {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) zs += a.v[e];
+    }
   }
   for (int c = V8n * 8 + threadIdx.x; c < V; c += NT) {
     const float a = bf2f(z[c]);
@@ -473,37 +481,52 @@ __global__ __launch_bounds__(NT) void k_ce_fwd(const uint16_t* __restrict__ logi
       mx = a;
     }
     sum += __expf(a - mx);
+    if (EXT) zs += a;
   }
   const float gmx = block_max(mx, red);
   sum = (mx == -INFINITY) ? 0.f : sum * __expf(mx - gmx);
   const float l = gmx + __logf(block_sum(sum, red));
+  if (EXT) zs = block_sum(zs, red);
   if (threadIdx.x == 0) {
     const long long y = labels[row];
     lse[row] = l;
-    loss[row] = (y == ignore_index) ? 0.f : l - bf2f(z[y]);
+    if (EXT)
+      loss[row] = (y == ignore_index) ? 0.f : (1.f - eps) * (l - bf2f(z[y])) + eps * (l - zs / (float)V) + zc * l * l;
+    else
+      loss[row] = (y == ignore_index) ? 0.f : l - bf2f(z[y]);
   }
 }
 
-// dz = (softmax(z) - onehot(y)) * scale[0], in place on z.
+// dz = (softmax(z) - onehot(y)) * scale[0], in place on z.  EXT:
+// dz = ((1 + 2*zc*lse)*softmax(z) - (1-eps)*onehot(y) - eps/V) * scale[0].
+template <bool EXT>
 __global__ __launch_bounds__(NT) void k_ce_bwd(uint16_t* __restrict__ logits, const long long* __restrict__ labels,
                                                const float* __restrict__ lse, const float* __restrict__ scale, int V,
-                                               long long ignore_index) {
+                                               long long ignore_index, float eps, float zc) {
   const long long row = blockIdx.x;
   uint16_t* z = logits + row * V;
   const long long y = labels[row];
   const float sc = (y == ignore_index) ? 0.f : scale[0];
   const float l = lse[row];
+  // per-row constants of the EXT form: dz = ka*exp(z - lse) - [c == y]*kb - kc
+  const float ka = (1.f + 2.f * zc * l) * sc, kb = (1.f - eps) * sc, kc = eps / (float)V * sc;
   const int V8n = V >> 3;
   for (int i = threadIdx.x; i < V8n; i += NT) {
     V8 a = ld8(z + i * 8);
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
       const int c = i * 8 + e;
-      a.v[e] = (__expf(a.v[e] - l) - (c == y ? 1.f : 0.f)) * sc;
+      if (EXT)
+        a.v[e] = ka * __expf(a.v[e] - l) - (c == y ? kb : 0.f) - kc;
+      else
+        a.v[e] = (__expf(a.v[e] - l) - (c == y ? 1.f : 0.f)) * sc;
     }
     st8(z + i * 8, a);
   }
-  for (int c = V8n * 8 + threadIdx.x; c < V; c += NT) z[c] = f2bf((__expf(bf2f(z[c]) - l) - (c == y ? 1.f : 0.f)) * sc);
+  for (int c = V8n * 8 + threadIdx.x; c < V; c += NT) {
+    const float p = __expf(bf2f(z[c]) - l);
+    z[c] = f2bf(EXT ? ka * p - (c == y ? kb : 0.f) - kc : (p - (c == y ? 1.f : 0.f)) * sc);
+  }
 }
 
 inline unsigned grid_for(long long work, int per_block = NT) {
@@ -650,8 +673,8 @@ PTO_API int pto_ce_fwd(const void* logits, const long long* labels, float* lse, 
                        long long ignore_index, hipStream_t s) {
   if (V % 8) return -1;
   if (M <= 0) return 0;
-  hipLaunchKernelGGL(k_ce_fwd, dim3((unsigned)M), dim3(NT), 0, s, (const uint16_t*)logits, labels, lse, loss, V,
-                     ignore_index);
+  hipLaunchKernelGGL(k_ce_fwd<false>, dim3((unsigned)M), dim3(NT), 0, s, (const uint16_t*)logits, labels, lse, loss, V,
+                     ignore_index, 0.f, 0.f);
   return (int)hipGetLastError();
 }
 
@@ -659,8 +682,27 @@ PTO_API int pto_ce_bwd(void* logits, const long long* labels, const float* lse, 
                        long long ignore_index, hipStream_t s) {
   if (V % 8) return -1;
   if (M <= 0) return 0;
-  hipLaunchKernelGGL(k_ce_bwd, dim3((unsigned)M), dim3(NT), 0, s, (uint16_t*)logits, labels, lse, scale, V,
-                     ignore_index);
+  hipLaunchKernelGGL(k_ce_bwd<false>, dim3((unsigned)M), dim3(NT), 0, s, (uint16_t*)logits, labels, lse, scale, V,
+                     ignore_index, 0.f, 0.f);
+  return (int)hipGetLastError();
+}
+
+// Cross entropy with label smoothing and z-loss (k_ce_fwd / k_ce_bwd, EXT).
+PTO_API int pto_ce_fwd_ex(const void* logits, const long long* labels, float* lse, float* loss, long long M, int V,
+                          long long ignore_index, float smoothing, float z_coef, hipStream_t s) {
+  if (V % 8) return -1;
+  if (M <= 0) return 0;
+  hipLaunchKernelGGL(k_ce_fwd<true>, dim3((unsigned)M), dim3(NT), 0, s, (const uint16_t*)logits, labels, lse, loss, V,
+                     ignore_index, smoothing, z_coef);
+  return (int)hipGetLastError();
+}
+
+PTO_API int pto_ce_bwd_ex(void* logits, const long long* labels, const float* lse, const float* scale, long long M,
+                          int V, long long ignore_index, float smoothing, float z_coef, hipStream_t s) {
+  if (V % 8) return -1;
+  if (M <= 0) return 0;
+  hipLaunchKernelGGL(k_ce_bwd<true>, dim3((unsigned)M), dim3(NT), 0, s, (uint16_t*)logits, labels, lse, scale, V,
+                     ignore_index, smoothing, z_coef);
   return (int)hipGetLastError();
 }
 

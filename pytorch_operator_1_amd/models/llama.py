@@ -184,7 +184,12 @@ def _rmsnorm_ref(x, w, eps):
 
 class Llama(nn.Module):
     def __init__(self, cfg: LlamaConfig | str = "llama3-8b", impl: str = "hip", device=None,
-                 dtype=torch.bfloat16, checkpoint: str = "none", init_std: float = 0.02):
+                 dtype=torch.bfloat16, checkpoint: str = "none", init_std: float = 0.02,
+                 label_smoothing: float = 0.0, z_loss: float = 0.0):
+        """``label_smoothing`` / ``z_loss``: options of the training loss
+        (:func:`..ops.llm.cross_entropy`).  After a forward with labels
+        ``last_z_loss`` is the detached z part of the loss,
+        ``z_loss * mean_valid(logsumexp^2)`` (``None`` when ``z_loss == 0``)."""
         super().__init__()
         if isinstance(cfg, str):
             cfg = CONFIGS[cfg]
@@ -192,7 +197,13 @@ class Llama(nn.Module):
             raise ValueError(f"impl must be hip|torch, got {impl}")
         if checkpoint not in ("none", "full"):
             raise ValueError("checkpoint must be none|full")
+        if not 0.0 <= label_smoothing < 1.0:
+            raise ValueError(f"label_smoothing must be in [0, 1), got {label_smoothing}")
+        if not z_loss >= 0.0:
+            raise ValueError(f"z_loss must be >= 0, got {z_loss}")
         self.cfg, self.impl, self.checkpoint = cfg, impl, checkpoint
+        self.label_smoothing, self.z_loss = float(label_smoothing), float(z_loss)
+        self.last_z_loss = None
         kw = dict(device=device, dtype=dtype)
         self.tok_emb = nn.Embedding(cfg.vocab_size, cfg.dim, **kw)
         self.layers = nn.ModuleList(LlamaBlock(cfg, **kw) for _ in range(cfg.n_layers))
@@ -277,13 +288,23 @@ class Llama(nn.Module):
             logits = F.linear(y, self._head_weight()) if self.lm_head is None else _lin(y, self.lm_head)
             if labels is None:
                 return logits.view(B, S, -1)
-            return llm.cross_entropy(logits, labels.reshape(-1))
+            loss, self.last_z_loss = llm.cross_entropy(logits, labels.reshape(-1), label_smoothing=self.label_smoothing,
+                                                       z_loss=self.z_loss, return_z=True)
+            return loss
         h = h + delta
         y = _rmsnorm_ref(h, self.norm, self.cfg.norm_eps)
         logits = F.linear(y, self._head_weight())
         if labels is None:
             return logits.view(B, S, -1)
-        return F.cross_entropy(logits.float(), labels.reshape(-1))
+        labels = labels.reshape(-1)
+        loss = F.cross_entropy(logits.float(), labels, label_smoothing=self.label_smoothing)
+        if self.z_loss:
+            valid = labels != -100  # F.cross_entropy's ignore_index
+            lse2 = torch.logsumexp(logits.float(), dim=-1).square()
+            z_part = self.z_loss * (lse2 * valid).sum() / valid.sum().clamp_min(1)
+            self.last_z_loss = z_part.detach()
+            loss = loss + z_part
+        return loss
 
 
 def synthetic_tokens(batch: int, seq_len: int, vocab: int, device, seed: int = 0):

@@ -145,6 +145,9 @@ _SIGS = {
     "pto_rope": [_P, _P, _P, _P, _L, _I, _I, _I, _I, _L, _I, _P],
     "pto_ce_fwd": [_P, _P, _P, _P, _L, _I, _L, _P],
     "pto_ce_bwd": [_P, _P, _P, _P, _L, _I, _L, _P],
+    # ... with label smoothing and z-loss (float smoothing, float z_coef)
+    "pto_ce_fwd_ex": [_P, _P, _P, _P, _L, _I, _L, _F, _F, _P],
+    "pto_ce_bwd_ex": [_P, _P, _P, _P, _L, _I, _L, _F, _F, _P],
     "pto_transpose_bf16": [_P, _P, _L, _L, _L, _L, _P],
     "pto_noop": [_I, _P],
     "pto_graph_upload": [_P, _P],

@@ -191,36 +191,60 @@ def rope_tables(seq_len: int, head_dim: int, theta: float, device, scaling: dict
 
 class _CrossEntropy(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, logits, labels, ignore_index):
+    def forward(ctx, logits, labels, ignore_index, smoothing, z_coef):
         logits = _req(logits, "cross_entropy")
         V = logits.shape[-1]
         M = logits.numel() // V
         labels = labels.reshape(M).to(torch.int64).contiguous()
         lse = torch.empty(M, device=logits.device, dtype=torch.float32)
         rows = torch.empty(M, device=logits.device, dtype=torch.float32)
-        _lib.check(_lib.lib().pto_ce_fwd(logits.data_ptr(), labels.data_ptr(), lse.data_ptr(), rows.data_ptr(), M, V,
-                                         ignore_index, _lib.stream_ptr(logits.device)), "ce_fwd")
-        count = (labels != ignore_index).sum().clamp_min(1).float()
+        ctx.ex = (smoothing, z_coef) if (smoothing or z_coef) else ()  # both 0: the plain kernels
+        fwd = _lib.lib().pto_ce_fwd_ex if ctx.ex else _lib.lib().pto_ce_fwd
+        _lib.check(fwd(logits.data_ptr(), labels.data_ptr(), lse.data_ptr(), rows.data_ptr(), M, V, ignore_index,
+                       *ctx.ex, _lib.stream_ptr(logits.device)), "ce_fwd")
+        valid = labels != ignore_index
+        count = valid.sum().clamp_min(1).float()
         ctx.save_for_backward(logits, labels, lse, count)
         ctx.ignore_index = ignore_index
-        return rows.sum() / count
+        loss = rows.sum() / count
+        if not z_coef:
+            return loss, None
+        # the z part of the loss, z_coef * mean_valid(lse^2), from the kernel's lse: [M] floats, no logits pass
+        z_part = z_coef * (lse.square() * valid).sum() / count
+        ctx.mark_non_differentiable(z_part)
+        return loss, z_part
 
     @staticmethod
-    def backward(ctx, gout):
+    def backward(ctx, gout, _gz=None):
         logits, labels, lse, count = ctx.saved_tensors
         V = logits.shape[-1]
         M = logits.numel() // V
         scale = (gout.float() / count).reshape(1)
         # logits is an intermediate owned by this op (the producing GEMM's
         # backward needs only its inputs), so the gradient overwrites it.
-        _lib.check(_lib.lib().pto_ce_bwd(logits.data_ptr(), labels.data_ptr(), lse.data_ptr(), scale.data_ptr(), M, V,
-                                         ctx.ignore_index, _lib.stream_ptr(logits.device)), "ce_bwd")
-        return logits, None, None
+        bwd = _lib.lib().pto_ce_bwd_ex if ctx.ex else _lib.lib().pto_ce_bwd
+        _lib.check(bwd(logits.data_ptr(), labels.data_ptr(), lse.data_ptr(), scale.data_ptr(), M, V, ctx.ignore_index,
+                       *ctx.ex, _lib.stream_ptr(logits.device)), "ce_bwd")
+        return logits, None, None, None, None
 
 
-def cross_entropy(logits, labels, ignore_index: int = -100):
-    """Mean token cross-entropy over non-ignored labels on bf16 logits."""
-    return _CrossEntropy.apply(logits, labels, ignore_index)
+def cross_entropy(logits, labels, ignore_index: int = -100, label_smoothing: float = 0.0, z_loss: float = 0.0,
+                  return_z: bool = False):
+    """Mean token cross-entropy over non-ignored labels on bf16 logits.
+
+    ``label_smoothing`` (eps) and ``z_loss`` (zc) extend the row loss to
+    ``(1-eps)*(lse - z[y]) + eps*(lse - mean(z)) + zc*lse^2``: the first two
+    terms are ``F.cross_entropy(..., label_smoothing=eps)``, the third is the
+    z-loss on the softmax normaliser.  Both at 0 run the plain kernels.
+    ``return_z=True`` returns ``(loss, z_part)``, ``z_part`` the detached
+    ``zc * mean_valid(lse^2)`` already contained in ``loss`` (a device scalar;
+    ``None`` when ``z_loss == 0``)."""
+    if not 0.0 <= label_smoothing < 1.0:
+        raise ValueError(f"cross_entropy: label_smoothing must be in [0, 1), got {label_smoothing}")
+    if not z_loss >= 0.0:
+        raise ValueError(f"cross_entropy: z_loss must be >= 0, got {z_loss}")
+    loss, z_part = _CrossEntropy.apply(logits, labels, ignore_index, float(label_smoothing), float(z_loss))
+    return (loss, z_part) if return_z else loss
 
 
 def flash_attention_supported(S: int, H: int, Hkv: int, head_dim: int) -> bool:

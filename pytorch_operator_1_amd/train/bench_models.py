@@ -81,6 +81,12 @@ def _clip_text(max_grad_norm):
     return f"global grad norm clipped to {max_grad_norm:g} on the device"
 
 
+def _loss_text(label_smoothing: float, z_loss: float = 0.0) -> str:
+    if not (label_smoothing or z_loss):
+        return "CE"
+    return f"CE label_smoothing={label_smoothing:g} z_loss={z_loss:g}"
+
+
 class CheckpointMixin:
     """Named tensors of the full training state (parameters, buffers,
     optimizer state) for :class:`..train.checkpoint.ShardedCheckpointer`,
@@ -154,10 +160,13 @@ class ResNetTrainer(CheckpointMixin):
     def __init__(self, device, batch_size: int = 256, image_size: int = 224, lr: float = 0.1,
                  momentum: float = 0.9, weight_decay: float = 1e-4, seed: int = 0, bucket_mb: float | None = None,
                  force_ddp: bool = False, graph: bool | None = None, max_grad_norm: float | None = None,
-                 grad_accum_steps: int = 1):
+                 grad_accum_steps: int = 1, label_smoothing: float = 0.0):
         from ..models.resnet import resnet50, synthetic_images
 
         self.grad_accum_steps = _accum_steps(grad_accum_steps)
+        if not 0.0 <= label_smoothing < 1.0:
+            raise ValueError(f"label_smoothing must be in [0, 1), got {label_smoothing}")
+        self.label_smoothing = float(label_smoothing)  # the ImageNet recipe: 0.1; fixed once a step is captured
         if graph is None:
             graph = os.environ.get("PTO_STEP_GRAPH", "0") == "1"
         if graph and self.grad_accum_steps > 1:
@@ -213,7 +222,7 @@ class ResNetTrainer(CheckpointMixin):
         with torch.cuda.graph(g):
             with torch.autocast(device_type="cuda", dtype=torch.bfloat16):
                 out = self.model(self.x)
-            loss = F.cross_entropy(out.float(), self.y)
+            loss = F.cross_entropy(out.float(), self.y, label_smoothing=self.label_smoothing)
             loss.backward()
             GradStash.assert_drained()
             self.bucketer.finish()
@@ -230,7 +239,7 @@ class ResNetTrainer(CheckpointMixin):
             with t.phase("forward"), torch.autocast(device_type=self.device.type, dtype=torch.bfloat16):
                 out = self.model(x)
             with t.phase("forward"):
-                loss = F.cross_entropy(out.float(), y)
+                loss = F.cross_entropy(out.float(), y, label_smoothing=self.label_smoothing)
             with t.phase("backward"):
                 loss.backward()
                 GradStash.assert_drained()  # host counter: no sibling conv1x1 gradient left parked
@@ -268,15 +277,21 @@ class ResNetTrainer(CheckpointMixin):
                 "step": (f"whole step replayed as one HIP graph (after {self.EAGER_STEPS} eager steps)"
                          if self.use_graph else "eager"),
                 "grad_clip": _clip_text(self.max_grad_norm),
-                "grad_accum": _accum_text(self.grad_accum_steps, self.bucketer)}
+                "grad_accum": _accum_text(self.grad_accum_steps, self.bucketer),
+                "loss": _loss_text(self.label_smoothing)}
 
 
 class LlamaTrainer(CheckpointMixin):
     def __init__(self, device, model: str = "llama3-8b", batch_size: int = 2, seq_len: int = 4096,
                  lr: float = 3e-4, weight_decay: float = 0.1, seed: int = 0, checkpoint: str = "none",
                  impl: str | None = None, bucket_mb: float | None = None, force_ddp: bool = False,
-                 max_grad_norm: float | None = None, grad_accum_steps: int = 1):
-        """``grad_accum_steps=N``: :meth:`step` stays ONE optimizer step and
+                 max_grad_norm: float | None = None, grad_accum_steps: int = 1, label_smoothing: float = 0.0,
+                 z_loss: float = 0.0):
+        """``label_smoothing`` / ``z_loss``: options of the training loss
+        (:class:`..models.llama.Llama`); :meth:`last_z_loss` is the z part of
+        the last step's loss.
+
+        ``grad_accum_steps=N``: :meth:`step` stays ONE optimizer step and
         runs N micro-batches of ``batch_size`` rows (forward, backward,
         ``bucketer.finish()``), summing their gradients in fp32 on the device
         (:class:`..parallel.ddp.GradBucketer`); optimizer, weight
@@ -296,7 +311,8 @@ class LlamaTrainer(CheckpointMixin):
         self.device = device
         self.batch_size, self.seq_len = batch_size, seq_len
         self.max_grad_norm = max_grad_norm  # global-norm clip (the Llama recipe: 1.0; inf: report only)
-        self.model = Llama(self.cfg, impl=impl, device=device, checkpoint=checkpoint)
+        self.model = Llama(self.cfg, impl=impl, device=device, checkpoint=checkpoint, label_smoothing=label_smoothing,
+                           z_loss=z_loss)
         self.model.train()
         # W^T copies for K-contiguous dgrad GEMMs (PTO_WT=0: plain F.linear backward;
         # with PTO_GEMM=1 the package's NN GEMM then reads W as stored, ops/gemm.py)
@@ -315,12 +331,13 @@ class LlamaTrainer(CheckpointMixin):
                                                     device, seed=seed)
         self._micro = list(zip(self.tokens.split(batch_size), self.labels.split(batch_size)))
         self._loss = None
+        self._z = None
         self.steps_done = 0
         self.timer = StepTimer(device, enabled=False)
 
     def step(self):
         t = self.timer
-        total = None
+        total = ztotal = None
         for tokens, labels in self._micro:
             with t.phase("forward"):
                 loss = self.model(tokens, labels)
@@ -329,8 +346,11 @@ class LlamaTrainer(CheckpointMixin):
             with t.phase("allreduce_wait"):  # not the last micro-batch: the fp32 accumulation, no collective
                 self.bucketer.finish()
             total = loss.detach() if total is None else total + loss.detach()
+            z = self.model.last_z_loss  # None when z_loss is off
+            ztotal = z if ztotal is None or z is None else ztotal + z
         if self.grad_accum_steps > 1:
             loss = total / self.grad_accum_steps  # on the device, no sync
+            ztotal = None if ztotal is None else ztotal / self.grad_accum_steps
         with t.phase("optimizer"):
             self.opt.step(grad_scale=self.bucketer.grad_scale, zero_grad=self.bucketer.optimizer_zeroes_grads,
                           max_grad_norm=self.max_grad_norm)
@@ -338,6 +358,7 @@ class LlamaTrainer(CheckpointMixin):
             if self.transposed_dgrad:
                 self.model.refresh_transposed()
         self._loss = loss.detach()
+        self._z = ztotal
         self.steps_done += 1
 
     def run(self, n: int):
@@ -346,6 +367,10 @@ class LlamaTrainer(CheckpointMixin):
 
     def last_loss(self):
         return None if self._loss is None else float(self._loss)
+
+    def last_z_loss(self):
+        """The z part of the last step's loss (mean over its micro-batches); None when ``z_loss`` is off."""
+        return _scalar(self._z)
 
     def last_grad_norm(self):
         return _scalar(self.opt.grad_norm) if self.max_grad_norm is not None else None
@@ -366,4 +391,5 @@ class LlamaTrainer(CheckpointMixin):
                 "checkpoint": self.model.checkpoint,
                 "dgrad": "W^T copies (K-contiguous dX GEMMs)" if self.transposed_dgrad else "F.linear",
                 "grad_clip": _clip_text(self.max_grad_norm),
-                "grad_accum": _accum_text(self.grad_accum_steps, self.bucketer)}
+                "grad_accum": _accum_text(self.grad_accum_steps, self.bucketer),
+                "loss": _loss_text(self.model.label_smoothing, self.model.z_loss)}

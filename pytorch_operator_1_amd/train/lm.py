@@ -17,6 +17,9 @@ but a restarted replica starts from step 0.  Here:
 * ``--grad-accum-steps N`` makes every step N micro-batches of
   ``--batch-size`` with one optimizer update (fp32 gradient sums on the
   device); checkpoints fall between optimizer steps and need nothing extra;
+* ``--label-smoothing F`` / ``--z-loss F`` set the options of the training
+  loss (the Llama cross entropy computes both inside its HIP kernels;
+  ``--z-loss`` is Llama only) and ``--z-loss`` logs the z part of the loss;
 * a collective failure exits 138 (retryable for ``restartPolicy: ExitCode``)
   exactly like the MNIST trainer, so kill/rejoin works for these models too.
 
@@ -66,7 +69,18 @@ def parse_args(argv=None):
     p.add_argument("--grad-accum-steps", type=int, default=1,
                    help="micro-batches of --batch-size per optimizer step, their gradients summed in fp32 on "
                         "the device (default 1: off); --steps counts optimizer steps")
+    p.add_argument("--label-smoothing", type=float, default=0.0,
+                   help="label smoothing of the cross entropy, in [0, 1) (default 0: off)")
+    p.add_argument("--z-loss", type=float, default=0.0,
+                   help="coefficient of the z-loss, z_loss * logsumexp(logits)^2 per token, added to the Llama "
+                        "loss and logged (default 0: off; about 1e-4 in bf16 LM recipes)")
     args = p.parse_args(argv)
+    if not 0.0 <= args.label_smoothing < 1.0:
+        p.error("--label-smoothing must be in [0, 1)")
+    if not args.z_loss >= 0.0:
+        p.error("--z-loss must be >= 0")
+    if args.z_loss > 0 and args.model == "resnet50":
+        p.error("--z-loss is for the Llama models")
     if args.grad_accum_steps < 1:
         p.error("--grad-accum-steps must be >= 1")
     if args.max_grad_norm is not None and not args.max_grad_norm >= 0:
@@ -80,11 +94,13 @@ def build(args, device):
     if args.model == "resnet50":
         kw = {} if args.lr is None else {"lr": args.lr}
         return ResNetTrainer(device, batch_size=args.batch_size or 64, image_size=args.image_size, seed=args.seed,
-                             max_grad_norm=args.max_grad_norm, grad_accum_steps=args.grad_accum_steps, **kw)
+                             max_grad_norm=args.max_grad_norm, grad_accum_steps=args.grad_accum_steps,
+                             label_smoothing=args.label_smoothing, **kw)
     kw = {} if args.lr is None else {"lr": args.lr}
     return LlamaTrainer(device, model=args.model, batch_size=args.batch_size or 2, seq_len=args.seq_len,
                         seed=args.seed, checkpoint=args.activation_checkpoint, max_grad_norm=args.max_grad_norm,
-                        grad_accum_steps=args.grad_accum_steps, **kw)
+                        grad_accum_steps=args.grad_accum_steps, label_smoothing=args.label_smoothing,
+                        z_loss=args.z_loss, **kw)
 
 
 def _main(argv=None):
@@ -129,6 +145,9 @@ def _main(argv=None):
             if args.max_grad_norm is not None:  # read here only: last_loss() has already synced
                 extra = {"grad_norm": trainer.last_grad_norm(), "clip_coef": trainer.last_clip_coef()}
                 clip = f"\tgrad_norm={extra['grad_norm']:.4f}"
+            if args.z_loss > 0:  # likewise after the sync
+                extra["z_loss"] = trainer.last_z_loss()
+                clip += f"\tz_loss={extra['z_loss']:.6f}"
             print(f"step {done}/{args.steps}\tloss={loss:.6f}{clip}\t{sps:.1f} samples/s", flush=True)
             metrics.emit(event="train", step=done, loss=loss, samples_per_sec=round(sps, 1),
                          step_seconds=(now - t_last) / steps_since, rank=rank, **extra)

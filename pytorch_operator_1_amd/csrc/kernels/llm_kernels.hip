@@ -10,6 +10,8 @@
 //   rope_fwd/bwd      in place on the q,k heads of the fused QKV GEMM output
 //   ce_fwd/bwd        vocab-wide cross entropy on bf16 logits (128256 columns),
 //                     gradient written in place into the logits buffer
+//   ce_eval/eval_accum  evaluation: per-row NLL and rank of the label in one read
+//                     of the logits, summed into an fp64 record on the device
 //
 // Rows are processed by one 256-thread block (4 waves); each thread moves
 // 8 bf16 (16 bytes) per access (Guideline 13).  bf16 is raw uint16_t.
@@ -529,6 +531,122 @@ __global__ __launch_bounds__(NT) void k_ce_bwd(uint16_t* __restrict__ logits, co
   }
 }
 
+// ---------------------------------------------------------------- evaluation
+// k_ce_eval: held-out metrics of one row of V logits (bf16), one block per
+// row, ONE pass.  The label y is known up front, so every thread first
+// reads zy = z[y] and the loop that builds the log-sum-exp (k_ce_fwd's
+// online max/sum over the same loads) also counts the logits that rank
+// ahead of the label,
+//   rank = #{c : z[c] > zy} + #{c < y : z[c] == zy}
+//        = #{c < y : z[c] >= zy} + #{c > y : z[c] > zy},
+// one compare per logit.  rank == 0 is argmax(z) == y with the first-index
+// tie rule of torch.argmax, rank < k is a top-k hit (ties at the label are
+// the rule for bf16 logits at V = 128256, not the exception).  The counts
+// are int32 from the compare to the store: exact for any V.
+//   row_loss[m] = lse - zy   (plain NLL: no smoothing, no z-loss)
+//   row_rank[m] = rank;  -1: y == ignore_index;  -2: y outside [0, V)
+// Rows of the last two kinds get row_loss = 0 and z[y] is never read.
+// V % 8 == 0 (the launcher refuses anything else): no scalar tail.
+__global__ __launch_bounds__(NT) void k_ce_eval(const uint16_t* __restrict__ logits, const long long* __restrict__ labels,
+                                                float* __restrict__ row_loss, int* __restrict__ row_rank, int V,
+                                                long long ignore_index) {
+  __shared__ float red[4];
+  __shared__ int redi[4];
+  const long long row = blockIdx.x;
+  const long long yl = labels[row];
+  if (yl == ignore_index || yl < 0 || yl >= V) {  // the whole block leaves: no barrier is skipped by a part of it
+    if (threadIdx.x == 0) {
+      row_loss[row] = 0.f;
+      row_rank[row] = (yl == ignore_index) ? -1 : -2;
+    }
+    return;
+  }
+  const int y = (int)yl;
+  const uint16_t* z = logits + row * V;
+  const float zy = bf2f(z[y]);
+  float mx = -INFINITY, sum = 0.f;
+  int cnt = 0;
+  const int V8n = V >> 3;
+  for (int i = threadIdx.x; i < V8n; i += NT) {
+    const V8 a = ld8(z + i * 8);
+    float lm = a.v[0];
+#pragma unroll
+    for (int e = 1; e < 8; ++e) lm = fmaxf(lm, a.v[e]);
+    if (lm > mx) {
+      sum *= __expf(mx - lm);
+      mx = lm;
+    }
+#pragma unroll
+    for (int e = 0; e < 8; ++e) sum += __expf(a.v[e] - mx);
+    const int c0 = i * 8;
+    if (c0 + 8 <= y) {  // all eight columns below the label: an equal logit wins the tie
+#pragma unroll
+      for (int e = 0; e < 8; ++e) cnt += (a.v[e] >= zy) ? 1 : 0;
+    } else if (c0 > y) {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) cnt += (a.v[e] > zy) ? 1 : 0;
+    } else {  // the chunk that holds the label
+#pragma unroll
+      for (int e = 0; e < 8; ++e) cnt += (c0 + e < y ? a.v[e] >= zy : a.v[e] > zy) ? 1 : 0;
+    }
+  }
+  const float gmx = block_max(mx, red);
+  sum = (mx == -INFINITY) ? 0.f : sum * __expf(mx - gmx);
+  const float l = gmx + __logf(block_sum(sum, red));
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o, 64);
+  if ((threadIdx.x & 63) == 0) redi[threadIdx.x >> 6] = cnt;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    row_loss[row] = l - zy;
+    row_rank[row] = redi[0] + redi[1] + redi[2] + redi[3];
+  }
+}
+
+// k_eval_accum: ONE workgroup folds the row_loss / row_rank of one
+// k_ce_eval call into the running record
+//   acc = {loss_sum, tokens, top1, topk, bad_labels}   (fp64)
+// Launches on one stream serialise, so successive calls accumulate.  Every
+// rank of a DDP job must report the same figures and a repeated evaluation
+// the same bits, so (as for k_grad_sqnorm_multi, optim_kernels.hip) the
+// order of every addition is fixed by M alone: no atomics.
+//   thread: rows t, t + EVT, ... in row order;  wave: 6 exchange steps;
+//   block: waves 0..EVT/64-1 in order, then one add into acc.
+// The counts are sums of 0/1 in fp64: exact below 2^53.
+constexpr int EVT = 1024;
+__global__ __launch_bounds__(EVT) void k_eval_accum(const float* __restrict__ row_loss,
+                                                    const int* __restrict__ row_rank, long long M, int k,
+                                                    double* __restrict__ acc) {
+  __shared__ double ws[EVT / 64][5];
+  double s[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+  for (long long m = threadIdx.x; m < M; m += EVT) {
+    const int r = row_rank[m];
+    if (r >= 0) {
+      s[0] += (double)row_loss[m];
+      s[1] += 1.0;
+      s[2] += (r == 0) ? 1.0 : 0.0;
+      s[3] += (r < k) ? 1.0 : 0.0;
+    } else if (r == -2) {
+      s[4] += 1.0;
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < 5; ++j) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) s[j] += __shfl_xor(s[j], o, 64);
+  }
+  if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+    for (int j = 0; j < 5; ++j) ws[threadIdx.x >> 6][j] = s[j];
+  }
+  __syncthreads();
+  if (threadIdx.x < 5) {
+    double tot = ws[0][threadIdx.x];
+    for (int w = 1; w < EVT / 64; ++w) tot += ws[w][threadIdx.x];
+    acc[threadIdx.x] += tot;
+  }
+}
+
 inline unsigned grid_for(long long work, int per_block = NT) {
   long long g = (work + per_block - 1) / per_block;
   if (g > 256 * 64) g = 256 * 64;  // grid-stride beyond 64 blocks per CU
@@ -703,6 +821,25 @@ PTO_API int pto_ce_bwd_ex(void* logits, const long long* labels, const float* ls
   if (M <= 0) return 0;
   hipLaunchKernelGGL(k_ce_bwd<true>, dim3((unsigned)M), dim3(NT), 0, s, (uint16_t*)logits, labels, lse, scale, V,
                      ignore_index, smoothing, z_coef);
+  return (int)hipGetLastError();
+}
+
+// Evaluation (k_ce_eval / k_eval_accum): row_loss [M] fp32 and row_rank [M]
+// int32 per row, then folded into acc = double[5] {loss_sum, tokens, top1,
+// topk, bad_labels}; acc is added to, the caller zeroes it.
+PTO_API int pto_ce_eval(const void* logits, const long long* labels, float* row_loss, int* row_rank, long long M, int V,
+                        long long ignore_index, hipStream_t s) {
+  if (V % 8) return -1;
+  if (M <= 0) return 0;
+  hipLaunchKernelGGL(k_ce_eval, dim3((unsigned)M), dim3(NT), 0, s, (const uint16_t*)logits, labels, row_loss, row_rank,
+                     V, ignore_index);
+  return (int)hipGetLastError();
+}
+
+PTO_API int pto_eval_accum(const float* row_loss, const int* row_rank, long long M, int k, double* acc,
+                           hipStream_t s) {
+  if (M <= 0) return 0;
+  hipLaunchKernelGGL(k_eval_accum, dim3(1), dim3(EVT), 0, s, row_loss, row_rank, M, k, acc);
   return (int)hipGetLastError();
 }
 

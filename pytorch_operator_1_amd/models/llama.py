@@ -267,8 +267,8 @@ class Llama(nn.Module):
     def _head_weight(self):
         return self.tok_emb.weight if self.lm_head is None else self.lm_head.weight
 
-    def forward(self, tokens: torch.Tensor, labels: torch.Tensor | None = None):
-        """``tokens`` [B, S] int64 -> mean CE loss if ``labels`` given, else logits."""
+    def _final_hidden(self, tokens: torch.Tensor):
+        """Blocks and final norm: the ``[B*S, dim]`` input of the head GEMM."""
         B, S = tokens.shape
         rope = self.rope(S, tokens.device)
         h = self.tok_emb(tokens).reshape(B * S, self.cfg.dim)
@@ -284,16 +284,46 @@ class Llama(nn.Module):
         if self.impl == "hip":
             from ..ops import llm
 
-            _, y = llm.add_rmsnorm(h, delta, self.norm, self.cfg.norm_eps)
-            logits = F.linear(y, self._head_weight()) if self.lm_head is None else _lin(y, self.lm_head)
+            return llm.add_rmsnorm(h, delta, self.norm, self.cfg.norm_eps)[1]
+        return _rmsnorm_ref(h + delta, self.norm, self.cfg.norm_eps)
+
+    def _head(self, y):
+        if self.impl == "hip" and self.lm_head is not None:
+            return _lin(y, self.lm_head)
+        return F.linear(y, self._head_weight())
+
+    @torch.no_grad()
+    def evaluate(self, tokens: torch.Tensor, labels: torch.Tensor, acc, head_chunk: int | None = 2048):
+        """Add the plain NLL and top-1 / top-k counts of ``tokens`` / ``labels``
+        ``[B, S]`` to ``acc`` (:class:`..ops.llm.EvalAccumulator`) without a
+        host sync.  The head GEMM (the path of :meth:`forward`) and the
+        accumulator run on at most ``head_chunk`` rows at a time, so the
+        ``[B*S, V]`` logits never exist at once (``None``: one chunk).
+        Leaves ``training``, ``last_z_loss`` and every ``.grad`` alone."""
+        if head_chunk is not None and head_chunk < 1:
+            raise ValueError(f"head_chunk must be >= 1 or None, got {head_chunk}")
+        y = self._final_hidden(tokens)
+        labels = labels.reshape(-1)
+        if labels.numel() != y.shape[0]:
+            raise ValueError(f"evaluate: {y.shape[0]} tokens, {labels.numel()} labels")
+        step = y.shape[0] if head_chunk is None else int(head_chunk)
+        for r0 in range(0, y.shape[0], max(step, 1)):
+            acc.update(self._head(y[r0:r0 + step]), labels[r0:r0 + step])
+        return acc
+
+    def forward(self, tokens: torch.Tensor, labels: torch.Tensor | None = None):
+        """``tokens`` [B, S] int64 -> mean CE loss if ``labels`` given, else logits."""
+        B, S = tokens.shape
+        y = self._final_hidden(tokens)
+        logits = self._head(y)
+        if self.impl == "hip":
+            from ..ops import llm
+
             if labels is None:
                 return logits.view(B, S, -1)
             loss, self.last_z_loss = llm.cross_entropy(logits, labels.reshape(-1), label_smoothing=self.label_smoothing,
                                                        z_loss=self.z_loss, return_z=True)
             return loss
-        h = h + delta
-        y = _rmsnorm_ref(h, self.norm, self.cfg.norm_eps)
-        logits = F.linear(y, self._head_weight())
         if labels is None:
             return logits.view(B, S, -1)
         labels = labels.reshape(-1)

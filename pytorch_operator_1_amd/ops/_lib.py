@@ -148,6 +148,9 @@ _SIGS = {
     # ... with label smoothing and z-loss (float smoothing, float z_coef)
     "pto_ce_fwd_ex": [_P, _P, _P, _P, _L, _I, _L, _F, _F, _P],
     "pto_ce_bwd_ex": [_P, _P, _P, _P, _L, _I, _L, _F, _F, _P],
+    # held-out evaluation: per-row NLL and label rank, then the fp64 record
+    "pto_ce_eval": [_P, _P, _P, _P, _L, _I, _L, _P],
+    "pto_eval_accum": [_P, _P, _L, _I, _P, _P],
     "pto_transpose_bf16": [_P, _P, _L, _L, _L, _L, _P],
     "pto_noop": [_I, _P],
     "pto_graph_upload": [_P, _P],

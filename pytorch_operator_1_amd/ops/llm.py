@@ -7,7 +7,8 @@ gradient add fused into the RMSNorm backward), :func:`swiglu`,
 :func:`rope_` (in place on the fused QKV projection), and
 :func:`cross_entropy` (vocab-wide CE on bf16 logits, gradient written in
 place into the logits buffer so no fp32 ``[tokens, 128256]`` tensor ever
-exists).
+exists).  :class:`EvalAccumulator` is the evaluation side of the cross
+entropy: plain NLL and top-1 / top-k counts summed on the device.
 """
 from __future__ import annotations
 
@@ -245,6 +246,105 @@ def cross_entropy(logits, labels, ignore_index: int = -100, label_smoothing: flo
         raise ValueError(f"cross_entropy: z_loss must be >= 0, got {z_loss}")
     loss, z_part = _CrossEntropy.apply(logits, labels, ignore_index, float(label_smoothing), float(z_loss))
     return (loss, z_part) if return_z else loss
+
+
+class EvalAccumulator:
+    """Held-out metrics of a language model, accumulated on the device.
+
+    The record is five fp64 numbers ``{loss_sum, tokens, top1, topk,
+    bad_labels}``.  :meth:`update` adds the rows of one ``[..., V]`` logits
+    tensor to it without a host sync: ``k_ce_eval`` writes each row's plain
+    NLL (never smoothing or z-loss) and the rank of its label,
+    ``#{z > z[y]} + #{c < y : z[c] == z[y]}`` -- ``rank == 0`` is
+    ``argmax == label`` with torch's first-index tie rule, ``rank < k`` a
+    top-k hit -- and ``k_eval_accum`` folds the rows in, in an order fixed by
+    the row count alone.  Rows labelled ``ignore_index`` are skipped
+    (rank -1); rows whose label is otherwise outside ``[0, V)`` are counted
+    as bad (rank -2), never dereferenced, and make :meth:`result` raise.
+
+    On HIP tensors the logits must be bf16 (no silent fallback).  On CPU
+    tensors the same five quantities come from torch ops on any float dtype:
+    the gloo/CPU trainer runs it and the GPU tests use it as the reference."""
+
+    def __init__(self, device, topk: int = 5, ignore_index: int = -100):
+        if int(topk) != topk or topk < 1:
+            raise ValueError(f"EvalAccumulator: topk must be an integer >= 1, got {topk}")
+        self.device = torch.device(device)
+        self.k = int(topk)
+        self.ignore_index = int(ignore_index)
+        self.acc = torch.zeros(5, device=self.device, dtype=torch.float64)
+
+    def reset(self):
+        self.acc.zero_()
+
+    @torch.no_grad()
+    def update(self, logits, labels, return_rows: bool = False):
+        """Add the rows of ``logits`` ``[..., V]`` / ``labels`` ``[...]`` to
+        the record; ``return_rows``: also return ``(row_loss, row_rank)``."""
+        V = logits.shape[-1]
+        M = logits.numel() // V if V else 0
+        if labels.numel() != M:
+            raise ValueError(f"EvalAccumulator: {M} rows of logits, {labels.numel()} labels")
+        if logits.is_cuda:
+            logits = _req(logits.detach(), "EvalAccumulator")
+            if logits.data_ptr() % 16:  # the kernel's 16-byte loads
+                logits = logits.clone()
+            labels = labels.reshape(M).to(device=logits.device, dtype=torch.int64).contiguous()
+            row_loss = torch.empty(M, device=logits.device, dtype=torch.float32)
+            row_rank = torch.empty(M, device=logits.device, dtype=torch.int32)
+            L, s = _lib.lib(), _lib.stream_ptr(logits.device)
+            _lib.check(L.pto_ce_eval(logits.data_ptr(), labels.data_ptr(), row_loss.data_ptr(), row_rank.data_ptr(),
+                                     M, V, self.ignore_index, s), "ce_eval")
+            _lib.check(L.pto_eval_accum(row_loss.data_ptr(), row_rank.data_ptr(), M, self.k, self.acc.data_ptr(), s),
+                       "eval_accum")
+        else:
+            row_loss, row_rank = self._rows_torch(logits.detach().reshape(M, V), labels.reshape(M).to(torch.int64))
+            ok = row_rank >= 0
+            self.acc += torch.stack([row_loss.double().sum(), ok.sum().double(), (row_rank == 0).sum().double(),
+                                     (ok & (row_rank < self.k)).sum().double(), (row_rank == -2).sum().double()])
+        return (row_loss, row_rank) if return_rows else None
+
+    def _rows_torch(self, z, y):
+        M, V = z.shape
+        if not z.is_floating_point():
+            raise TypeError(f"EvalAccumulator: float logits required (got {z.dtype})")
+        ignored = y == self.ignore_index
+        valid = (y >= 0) & (y < V) & ~ignored
+        yc = torch.where(valid, y, torch.zeros_like(y))[:, None]  # never index with a bad label
+        zy = z.gather(1, yc) if V else z.new_zeros(M, 1)
+        idx = torch.arange(V, device=z.device)[None, :]
+        rank = (z > zy).sum(1) + ((z == zy) & (idx < yc)).sum(1)
+        nll = torch.logsumexp(z.float(), dim=-1) - zy[:, 0].float()
+        row_loss = torch.where(valid, nll, torch.zeros_like(nll))
+        bad = torch.where(ignored, torch.full_like(y, -1), torch.full_like(y, -2))
+        return row_loss, torch.where(valid, rank, bad).to(torch.int32)
+
+    def all_reduce(self, group=None):
+        """Sum the record over the ranks (one collective); nothing to do
+        when torch.distributed is not initialised."""
+        import torch.distributed as dist
+
+        if dist.is_available() and dist.is_initialized():
+            dist.all_reduce(self.acc, op=dist.ReduceOp.SUM, group=group)
+
+    def result(self) -> dict:
+        """The metrics of everything added since :meth:`reset` (the only
+        host sync): mean NLL, its exp, top-1 / top-k accuracy as fractions."""
+        loss_sum, tokens, top1, topk, bad = self.acc.tolist()
+        if bad > 0:
+            raise ValueError(f"EvalAccumulator: {int(bad)} labels are neither ignore_index ({self.ignore_index}) "
+                             f"nor inside the vocabulary")
+        n = int(tokens)
+        if n == 0:
+            return {"loss": float("nan"), "ppl": float("nan"), "top1": 0.0, "topk": 0.0, "k": self.k, "tokens": 0}
+        import math
+
+        loss = loss_sum / n
+        try:
+            ppl = math.exp(loss)
+        except OverflowError:
+            ppl = float("inf")
+        return {"loss": loss, "ppl": ppl, "top1": top1 / n, "topk": topk / n, "k": self.k, "tokens": n}
 
 
 def flash_attention_supported(S: int, H: int, Hkv: int, head_dim: int) -> bool:

@@ -332,6 +332,9 @@ class LlamaTrainer(CheckpointMixin):
         self._micro = list(zip(self.tokens.split(batch_size), self.labels.split(batch_size)))
         self._loss = None
         self._z = None
+        self._seed = seed
+        self._heldout = []  # evaluate(split="heldout")'s batches, made on first use
+        self._eval = None
         self.steps_done = 0
         self.timer = StepTimer(device, enabled=False)
 
@@ -371,6 +374,56 @@ class LlamaTrainer(CheckpointMixin):
     def last_z_loss(self):
         """The z part of the last step's loss (mean over its micro-batches); None when ``z_loss`` is off."""
         return _scalar(self._z)
+
+    def _heldout_batches(self, n: int):
+        """The first ``n`` held-out batches of ``batch_size x seq_len``, made
+        on first use and kept.  Batch i of rank r is seeded from (seed, r, i)
+        through a hash, so it differs from the training batch (seeded with
+        ``seed`` itself) and from every other rank's and index's."""
+        import hashlib
+
+        import torch.distributed as dist
+
+        from ..models.llama import synthetic_tokens
+
+        rank = dist.get_rank() if dist.is_available() and dist.is_initialized() else 0
+        while len(self._heldout) < n:
+            key = f"heldout/{self._seed}/{rank}/{len(self._heldout)}".encode()
+            s = int.from_bytes(hashlib.sha256(key).digest()[:8], "little") >> 1
+            self._heldout.append(synthetic_tokens(self.batch_size, self.seq_len, self.cfg.vocab_size, self.device,
+                                                  seed=s))
+        return self._heldout[:n]
+
+    def evaluate(self, batches: int = 1, split: str = "heldout", topk: int = 5, head_chunk: int | None = 2048) -> dict:
+        """Plain NLL, perplexity and top-1 / top-``topk`` accuracy of the
+        current weights, accumulated on the device
+        (:class:`..ops.llm.EvalAccumulator`): ``split="heldout"`` over
+        ``batches`` fixed synthetic batches the model never trains on,
+        ``split="train"`` over the training micro-batches.  Under DDP the
+        record is all-reduced, so every rank returns the same dict (kept for
+        :meth:`last_eval`).  Reads the model and writes nothing training
+        reads: weights, optimizer state, ``W^T`` copies, ``steps_done`` and
+        the RNG streams are as before."""
+        from ..ops.llm import EvalAccumulator
+
+        if split == "heldout":
+            if int(batches) != batches or batches < 1:
+                raise ValueError(f"evaluate: batches must be an integer >= 1, got {batches}")
+            data = self._heldout_batches(int(batches))
+        elif split == "train":
+            data = self._micro
+        else:
+            raise ValueError(f"evaluate: split must be heldout|train, got {split!r}")
+        acc = EvalAccumulator(self.device, topk=topk)
+        for tokens, labels in data:
+            self.model.evaluate(tokens, labels, acc, head_chunk=head_chunk)
+        acc.all_reduce()
+        self._eval = acc.result()
+        return self._eval
+
+    def last_eval(self):
+        """The dict of the last :meth:`evaluate`; None before the first."""
+        return self._eval
 
     def last_grad_norm(self):
         return _scalar(self.opt.grad_norm) if self.max_grad_norm is not None else None

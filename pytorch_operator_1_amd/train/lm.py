@@ -20,6 +20,14 @@ but a restarted replica starts from step 0.  Here:
 * ``--label-smoothing F`` / ``--z-loss F`` set the options of the training
   loss (the Llama cross entropy computes both inside its HIP kernels;
   ``--z-loss`` is Llama only) and ``--z-loss`` logs the z part of the loss;
+* ``--eval-interval N`` (Llama only) evaluates the model every N optimizer
+  steps and after the last one on ``--eval-batches K`` held-out synthetic
+  batches it never trains on: plain NLL (no smoothing, no z-loss),
+  perplexity, top-1 and top-``--eval-topk`` accuracy, accumulated on the
+  device with one all-reduce and one sync per evaluation, the head GEMM in
+  chunks of ``--eval-head-chunk R`` rows so the full logits never exist.
+  It prints an ``eval step`` line, emits an ``eval`` metrics event, and its
+  time stays out of the samples/s of the training log;
 * a collective failure exits 138 (retryable for ``restartPolicy: ExitCode``)
   exactly like the MNIST trainer, so kill/rejoin works for these models too.
 
@@ -74,7 +82,22 @@ def parse_args(argv=None):
     p.add_argument("--z-loss", type=float, default=0.0,
                    help="coefficient of the z-loss, z_loss * logsumexp(logits)^2 per token, added to the Llama "
                         "loss and logged (default 0: off; about 1e-4 in bf16 LM recipes)")
+    p.add_argument("--eval-interval", type=int, default=0,
+                   help="evaluate the Llama model on held-out synthetic batches every N optimizer steps and after "
+                        "the last one: plain NLL, perplexity, top-1 / top-k accuracy, accumulated on the device "
+                        "(default 0: off)")
+    p.add_argument("--eval-batches", type=int, default=1, help="held-out batches of --batch-size per evaluation")
+    p.add_argument("--eval-topk", type=int, default=5, help="k of the top-k accuracy")
+    p.add_argument("--eval-head-chunk", type=int, default=2048,
+                   help="rows of logits alive at once during evaluation (the head GEMM runs per chunk)")
     args = p.parse_args(argv)
+    if args.eval_interval < 0:
+        p.error("--eval-interval must be >= 0")
+    if args.eval_batches < 1 or args.eval_topk < 1 or args.eval_head_chunk < 1:
+        p.error("--eval-batches, --eval-topk and --eval-head-chunk must be >= 1")
+    if args.model == "resnet50" and (args.eval_interval or args.eval_batches != 1 or args.eval_topk != 5
+                                     or args.eval_head_chunk != 2048):
+        p.error("--eval-interval / --eval-batches / --eval-topk / --eval-head-chunk are for the Llama models")
     if not 0.0 <= args.label_smoothing < 1.0:
         p.error("--label-smoothing must be in [0, 1)")
     if not args.z_loss >= 0.0:
@@ -101,6 +124,21 @@ def build(args, device):
                         seed=args.seed, checkpoint=args.activation_checkpoint, max_grad_norm=args.max_grad_norm,
                         grad_accum_steps=args.grad_accum_steps, label_smoothing=args.label_smoothing,
                         z_loss=args.z_loss, **kw)
+
+
+def _evaluate(args, trainer, device, metrics, done: int, rank: int) -> float:
+    """One held-out evaluation after optimizer step ``done``: print and emit
+    it, return the seconds it took (the training steps before it are
+    finished first, so none of their time is counted as evaluation)."""
+    if device.type == "cuda":
+        torch.cuda.synchronize(device)
+    t0 = time.time()
+    ev = trainer.evaluate(batches=args.eval_batches, topk=args.eval_topk, head_chunk=args.eval_head_chunk)
+    print(f"eval step {done}\tloss={ev['loss']:.6f}\tppl={ev['ppl']:.4f}\ttop1={ev['top1']:.6f}\t"
+          f"top{ev['k']}={ev['topk']:.6f}\ttokens={ev['tokens']}", flush=True)
+    metrics.emit(event="eval", step=done, loss=ev["loss"], ppl=ev["ppl"], top1=ev["top1"], topk=ev["topk"],
+                 k=ev["k"], tokens=ev["tokens"], rank=rank)
+    return time.time() - t0
 
 
 def _main(argv=None):
@@ -152,6 +190,8 @@ def _main(argv=None):
             metrics.emit(event="train", step=done, loss=loss, samples_per_sec=round(sps, 1),
                          step_seconds=(now - t_last) / steps_since, rank=rank, **extra)
             t_last, steps_since = now, 0
+        if args.eval_interval and (done % args.eval_interval == 0 or done == args.steps):
+            t_last += _evaluate(args, trainer, device, metrics, done, rank)  # outside the throughput window
         if saver and args.checkpoint_interval and done % args.checkpoint_interval == 0 and done < args.steps:
             saver.save(done, trainer.checkpoint_tensors(), trainer.checkpoint_meta())
     if saver:

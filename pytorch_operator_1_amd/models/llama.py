@@ -23,6 +23,12 @@ large-model DDP config, built MI355X-first:
   activations (~4.4 MB/token without checkpointing), so a DDP replica
   holds 16-32k tokens per step with no sharding at all.
 
+* Generation: :class:`KVCache`, :meth:`Llama.prefill`,
+  :meth:`Llama.decode_step` and :meth:`Llama.generate` -- one new token per
+  row against cached K/V, on the kernels of ``csrc/kernels/decode.hip``
+  (cache append, split-KV decode attention, sampler), every length and
+  counter on the device so a step replays from a captured graph.
+
 ``impl="torch"`` is a plain PyTorch implementation of the same math used as
 the numerics reference (and for CPU tests).
 """
@@ -37,7 +43,8 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 # impl="hip" attention: "hip" = csrc/kernels/attention.hip (head_dim 128,
-# S % 128 == 0; other shapes fall back to SDPA), "sdpa" = ROCm SDPA.
+# S % 128 == 0; other shapes fall back to SDPA), "sdpa" = ROCm SDPA.  The
+# decode step follows the same switch (csrc/kernels/decode.hip or SDPA).
 ATTN_IMPL = os.environ.get("PTO_ATTN", "hip")
 
 
@@ -78,6 +85,9 @@ CONFIGS = {
     "llama3-1b": LlamaConfig(dim=2048, n_layers=16, n_heads=32, n_kv_heads=8, ffn_dim=8192),
     "llama3-tiny": LlamaConfig(dim=256, n_layers=2, n_heads=8, n_kv_heads=2, vocab_size=1024, ffn_dim=512,
                                max_seq_len=256),
+    # head_dim 128: small enough for CLI tests, yet on the owned attention kernels (training and decode)
+    "llama3-mini": LlamaConfig(dim=256, n_layers=2, n_heads=2, n_kv_heads=1, vocab_size=1024, ffn_dim=512,
+                               max_seq_len=512),
 }
 
 
@@ -112,7 +122,7 @@ class LlamaBlock(nn.Module):
         o = F.scaled_dot_product_attention(q, k, v, is_causal=True, enable_gqa=c.n_kv_heads != c.n_heads)
         return o.transpose(1, 2).reshape(B * S, c.n_heads * hd)
 
-    def forward_hip(self, h, delta, rope, B, S):
+    def forward_hip(self, h, delta, rope, B, S, kv=None):
         from ..ops import llm
 
         c = self.cfg
@@ -122,6 +132,8 @@ class LlamaBlock(nn.Module):
             h, y = llm.add_rmsnorm(h, delta, self.attn_norm, c.norm_eps)
         qkv = _lin(y, self.wqkv)
         qkv = llm.rope_(qkv, rope[0], rope[1], S, c.n_heads + c.n_kv_heads, c.head_dim)
+        if kv is not None:  # prefill: the rotated K and the V of this layer
+            kv.append(qkv)
         if ATTN_IMPL == "hip" and llm.flash_attention_supported(S, c.n_heads, c.n_kv_heads, c.head_dim):
             ctx = llm.flash_attention(qkv, B, S, c.n_heads, c.n_kv_heads)  # [B*S, H*128], no transposes
         else:
@@ -136,7 +148,7 @@ class LlamaBlock(nn.Module):
         mlp = _lin(llm.swiglu(_lin(y, self.w13, st), st), self.w2)
         return h, mlp
 
-    def forward_torch(self, h, delta, rope, B, S):
+    def forward_torch(self, h, delta, rope, B, S, kv=None):
         c = self.cfg
         if delta is not None:
             h = h + delta
@@ -148,12 +160,70 @@ class LlamaBlock(nn.Module):
         sin = torch.cat([rope[1], rope[1]], -1)[None, :, None, :]
         rot = (rot * cos + _rotate_half(rot) * sin).to(qkv.dtype).reshape(B * S, nr)
         qkv = torch.cat([rot, qkv[:, nr:]], dim=1)
+        if kv is not None:
+            kv.append(qkv)
         attn = F.linear(self._attend(qkv, B, S), self.wo.weight)
         h = h + attn
         y = _rmsnorm_ref(h, self.ffn_norm, c.norm_eps)
         g, u = F.linear(y, self.w13.weight).chunk(2, dim=-1)
         mlp = F.linear(F.silu(g) * u, self.w2.weight)
         return h, mlp
+
+    def decode(self, h, delta, rope, cache, layer: int, hip: bool):
+        """One new token per batch row (``h`` [B, dim]) against the cache:
+        the block of :meth:`forward_hip` / :meth:`forward_torch` with
+        ``M = B``, the new K/V appended at ``cache.lens`` and the attention
+        over ``cache.lens + 1`` keys."""
+        from ..ops import llm
+
+        c = self.cfg
+        k, v = cache.k[layer], cache.v[layer]
+        if hip:
+            if delta is None:
+                y = llm.rmsnorm(h, self.attn_norm, c.norm_eps)
+            else:
+                h, y = llm.add_rmsnorm(h, delta, self.attn_norm, c.norm_eps)
+            qkv = _lin(y, self.wqkv)
+            llm.rope_kv_append(qkv, rope[0], rope[1], k, v, cache.lens, c.n_heads, c.n_kv_heads)
+            ctx = llm.attention_decode(qkv, k, v, cache.lens_incl, c.n_heads, c.n_kv_heads,
+                                       impl="sdpa" if ATTN_IMPL == "sdpa" else None)
+            h, y = llm.add_rmsnorm(h, _lin(ctx, self.wo), self.ffn_norm, c.norm_eps)
+            return h, _lin(llm.swiglu(_lin(y, self.w13)), self.w2)
+        if delta is not None:
+            h = h + delta
+        y = _rmsnorm_ref(h, self.attn_norm, c.norm_eps)
+        qkv = F.linear(y, self.wqkv.weight)
+        llm.rope_kv_append(qkv, rope[0], rope[1], k, v, cache.lens, c.n_heads, c.n_kv_heads, impl="torch")
+        ctx = llm.attention_decode(qkv, k, v, cache.lens_incl, c.n_heads, c.n_kv_heads, impl="torch")
+        h = h + F.linear(ctx, self.wo.weight)
+        y = _rmsnorm_ref(h, self.ffn_norm, c.norm_eps)
+        g, u = F.linear(y, self.w13.weight).chunk(2, dim=-1)
+        return h, F.linear(F.silu(g) * u, self.w2.weight)
+
+
+class KVCache:
+    """The state of one generation: per layer the rotated keys and the values
+    of ``batch`` rows, bf16 (``dtype``) ``[batch, n_kv_heads, max_len,
+    head_dim]`` so one head's keys are contiguous, and the device-side
+    bookkeeping -- ``lens`` int32 ``[batch]`` (keys held per row), ``step``
+    int32 ``[1]`` (tokens emitted), ``done`` int32 ``[batch]`` (row has
+    emitted ``eos_id``).  Nothing past ``lens[b]`` is ever read."""
+
+    def __init__(self, cfg: LlamaConfig, batch: int, max_len: int, device=None, dtype=torch.bfloat16):
+        if batch < 1 or max_len < 1:
+            raise ValueError(f"KVCache: batch and max_len must be >= 1, got {batch}, {max_len}")
+        self.cfg, self.batch, self.max_len = cfg, int(batch), int(max_len)
+        shape = (self.batch, cfg.n_kv_heads, self.max_len, cfg.head_dim)
+        self.k = [torch.zeros(shape, device=device, dtype=dtype) for _ in range(cfg.n_layers)]
+        self.v = [torch.zeros(shape, device=device, dtype=dtype) for _ in range(cfg.n_layers)]
+        self.lens = torch.zeros(self.batch, device=device, dtype=torch.int32)
+        self.lens_incl = torch.zeros(self.batch, device=device, dtype=torch.int32)  # lens + 1 during a decode step
+        self.step = torch.zeros(1, device=device, dtype=torch.int32)
+        self.done = torch.zeros(self.batch, device=device, dtype=torch.int32)
+
+    def reset(self):
+        for t in (self.lens, self.lens_incl, self.step, self.done):
+            t.zero_()
 
 
 def _lin(x, mod: nn.Linear, tstash=None):
@@ -267,8 +337,9 @@ class Llama(nn.Module):
     def _head_weight(self):
         return self.tok_emb.weight if self.lm_head is None else self.lm_head.weight
 
-    def _final_hidden(self, tokens: torch.Tensor):
-        """Blocks and final norm: the ``[B*S, dim]`` input of the head GEMM."""
+    def _final_hidden(self, tokens: torch.Tensor, kv=None):
+        """Blocks and final norm: the ``[B*S, dim]`` input of the head GEMM
+        (``kv``: a list that receives every layer's rotated QKV, for prefill)."""
         B, S = tokens.shape
         rope = self.rope(S, tokens.device)
         h = self.tok_emb(tokens).reshape(B * S, self.cfg.dim)
@@ -279,6 +350,8 @@ class Llama(nn.Module):
                 from torch.utils.checkpoint import checkpoint
 
                 h, delta = checkpoint(fn, h, delta, rope, B, S, use_reentrant=False)
+            elif kv is not None:
+                h, delta = fn(h, delta, rope, B, S, kv)
             else:
                 h, delta = fn(h, delta, rope, B, S)
         if self.impl == "hip":
@@ -310,6 +383,138 @@ class Llama(nn.Module):
         for r0 in range(0, y.shape[0], max(step, 1)):
             acc.update(self._head(y[r0:r0 + step]), labels[r0:r0 + step])
         return acc
+
+    @torch.no_grad()
+    def prefill(self, tokens: torch.Tensor, lens: torch.Tensor | None, cache: KVCache):
+        """Run the right-padded prompts ``tokens`` [B, P] through the training
+        forward path, copy every layer's rotated K and its V into ``cache``
+        and set ``cache.lens`` to ``lens`` (int32 [B] on the device; None: P
+        for every row).  Returns the logits ``[B, V]`` at each row's last real
+        position.  Causality keeps the padding out of every real position,
+        and what the padding leaves in the cache lies past ``lens``."""
+        B, P = tokens.shape
+        c = self.cfg
+        if B != cache.batch or P > cache.max_len:
+            raise ValueError(f"prefill: {B} x {P} prompts do not fit a {cache.batch} x {cache.max_len} cache")
+        if lens is None:
+            lens = torch.full((B,), P, device=tokens.device, dtype=torch.int32)
+        kv = []
+        y = self._final_hidden(tokens, kv=kv)
+        H, Hkv = c.n_heads, c.n_kv_heads
+        for i, qkv in enumerate(kv):
+            v4 = qkv.view(B, P, H + 2 * Hkv, c.head_dim)
+            cache.k[i][:, :, :P].copy_(v4[:, :, H:H + Hkv].transpose(1, 2))
+            cache.v[i][:, :, :P].copy_(v4[:, :, H + Hkv:].transpose(1, 2))
+        cache.reset()
+        cache.lens.copy_(lens)
+        last = (lens.long() - 1).clamp(0, P - 1)[:, None, None].expand(B, 1, c.dim)
+        return self._head(y.view(B, P, c.dim).gather(1, last)[:, 0].contiguous())
+
+    @torch.no_grad()
+    def decode_step(self, cur: torch.Tensor, cache: KVCache):
+        """Logits ``[B, V]`` of the next position given one new token ``cur``
+        [B] per row: its K/V are appended at ``cache.lens`` and it attends to
+        the ``cache.lens + 1`` keys then held.  ``cache.lens`` itself is
+        advanced by the sampler (:func:`..ops.llm.sample`), not here.  Every
+        op takes its lengths from the device, so the step can be captured in
+        a graph and replayed."""
+        hip = self.impl == "hip"
+        rope = self.rope(cache.max_len, cur.device)
+        torch.add(cache.lens, 1, out=cache.lens_incl)
+        h = self.tok_emb(cur)
+        delta = None
+        for i, blk in enumerate(self.layers):
+            h, delta = blk.decode(h, delta, rope, cache, i, hip)
+        if hip:
+            from ..ops import llm
+
+            y = llm.add_rmsnorm(h, delta, self.norm, self.cfg.norm_eps)[1]
+        else:
+            y = _rmsnorm_ref(h + delta, self.norm, self.cfg.norm_eps)
+        return self._head(y)
+
+    @torch.no_grad()
+    def generate(self, prompts: torch.Tensor, prompt_lens=None, max_new_tokens: int = 16, temperature: float = 0.0,
+                 top_k: int = 0, eos_id: int | None = None, seed: int = 0, graph: bool = False,
+                 return_logits: bool = False, cache: KVCache | None = None):
+        """Generate ``max_new_tokens`` tokens after each prompt: ``[B,
+        max_new_tokens]`` int64 on the device (with ``return_logits`` also the
+        ``[B, max_new_tokens, V]`` logits each token was chosen from).
+
+        ``prompts`` [B, P] is right-padded, ``prompt_lens`` the real lengths
+        as host integers (None: P for every row).  Prefill fills the KV cache
+        (``cache``: one to reuse; default a new one of exactly the length
+        needed), then every token costs one :meth:`decode_step` and one
+        :func:`..ops.llm.sample`: greedy at ``temperature == 0``, else
+        temperature / top-k sampling.  All uniforms are drawn once, before
+        the loop, as ``[max_new_tokens, B]`` from a device generator seeded
+        with ``seed`` and indexed by the device step counter, so the result
+        is a function of (weights, prompts, options, seed).  A row that emits
+        ``eos_id`` keeps emitting it.  Nothing in the loop syncs with the
+        host.  ``graph=True`` warms one step eagerly, restores the step state,
+        captures decode_step + sample + advance once and replays it for every
+        token after the first; it returns the tokens of ``graph=False``.
+
+        Leaves ``training``, every ``.grad`` and ``last_z_loss`` alone.
+        Raises ValueError when ``max(prompt_lens) + max_new_tokens`` exceeds
+        ``cfg.max_seq_len`` or the cache."""
+        from ..ops import llm
+
+        B, P = prompts.shape
+        n_new = int(max_new_tokens)
+        if n_new < 1:
+            raise ValueError(f"generate: max_new_tokens must be >= 1, got {max_new_tokens}")
+        host_lens = [P] * B if prompt_lens is None else [int(x) for x in prompt_lens]
+        if len(host_lens) != B or min(host_lens) < 1 or max(host_lens) > P:
+            raise ValueError(f"generate: prompt_lens must be {B} integers in [1, {P}]")
+        need = max(host_lens) + n_new
+        if need > self.cfg.max_seq_len:
+            raise ValueError(f"generate: {max(host_lens)} prompt + {n_new} new tokens exceed max_seq_len "
+                             f"{self.cfg.max_seq_len}")
+        dev = prompts.device
+        if cache is None:
+            cache = KVCache(self.cfg, B, max(need, P), dev, self.tok_emb.weight.dtype)
+        elif cache.batch != B or need > cache.max_len or P > cache.max_len:
+            raise ValueError(f"generate: {B} rows of {need} tokens exceed the {cache.batch} x {cache.max_len} cache")
+        lens = torch.tensor(host_lens, dtype=torch.int32).to(dev)
+        u = None
+        if temperature > 0:
+            u = torch.rand(n_new, B, device=dev, dtype=torch.float32,
+                           generator=torch.Generator(device=dev).manual_seed(int(seed)))
+        out = torch.zeros(B, n_new, device=dev, dtype=torch.int64)
+        cur = torch.zeros(B, device=dev, dtype=torch.int64)
+        kept = torch.empty(B, n_new, self.cfg.vocab_size, device=dev, dtype=self.tok_emb.weight.dtype) \
+            if return_logits else None
+        opts = dict(u=u, temperature=temperature, top_k=top_k, cur=cur, out=out, step=cache.step, done=cache.done,
+                    eos_id=eos_id, advance=True, impl=None if self.impl == "hip" else "torch")
+
+        logits = self.prefill(prompts, lens, cache)
+        if kept is not None:
+            kept[:, 0].copy_(logits)
+        llm.sample(logits, **opts)  # the first token is not in the cache yet: lens stays
+
+        def one_step():
+            z = self.decode_step(cur, cache)
+            llm.sample(z, lens=cache.lens, **opts)
+            return z
+
+        use_graph = bool(graph) and dev.type == "cuda" and n_new > 1
+        if use_graph:
+            state = [t.clone() for t in (cur, cache.step, cache.lens, cache.done)]
+            one_step()  # library handles, workspaces, the rope table; then put the step state back
+            for t, saved in zip((cur, cache.step, cache.lens, cache.done), state):
+                t.copy_(saved)
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):
+                z = one_step()
+        for t in range(1, n_new):
+            if use_graph:
+                g.replay()
+            else:
+                z = one_step()
+            if kept is not None:
+                kept[:, t].copy_(z)
+        return (out, kept) if return_logits else out
 
     def forward(self, tokens: torch.Tensor, labels: torch.Tensor | None = None):
         """``tokens`` [B, S] int64 -> mean CE loss if ``labels`` given, else logits."""

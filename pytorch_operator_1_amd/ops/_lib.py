@@ -30,7 +30,7 @@ HIPCC = os.environ.get("HIPCC", shutil.which("hipcc") or "/opt/rocm/bin/hipcc")
 
 HIP_SOURCES = ("kernels/mnist_kernels.hip", "kernels/common_kernels.hip", "kernels/optim_kernels.hip",
                "kernels/llm_kernels.hip", "kernels/attention.hip", "kernels/bn_kernels.hip", "kernels/conv3x3.hip",
-               "kernels/conv3x3_wgrad.hip", "kernels/gemm_bf16.hip", "comm/xgmi_allreduce.hip")
+               "kernels/conv3x3_wgrad.hip", "kernels/gemm_bf16.hip", "comm/xgmi_allreduce.hip", "kernels/decode.hip")
 
 _lock = threading.Lock()
 # launchers return an int hipError; these few return something else
@@ -186,6 +186,12 @@ _SIGS = {
     # causal GQA flash attention, head_dim 128 (csrc/kernels/attention.hip)
     "pto_attn_fwd": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _L, _L, _L, _L, _F, _P],
     "pto_attn_bwd": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _I, _I, _I, _I, _L, _L, _L, _L, _F, _P],
+    # KV-cache generation: cache append, split-KV decode attention, sampler (csrc/kernels/decode.hip)
+    "pto_rope_kv_append": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
+    "pto_attn_decode_supported": [_I, _I, _I],
+    "pto_attn_decode_chunk": [_I, _I],
+    "pto_attn_decode": [_P, _L, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _P],
+    "pto_sample": [_P, _P, _P, _P, _I, _P, _P, _I, _I, _F, _I, _L, _I, _P, _P],
     # xGMI peer all-reduce (csrc/comm/xgmi_allreduce.hip)
     "pto_ar_ipc_handle_size": [],
     "pto_ar_flag_bytes": [_I],

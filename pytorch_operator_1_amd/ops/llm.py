@@ -9,6 +9,11 @@ gradient add fused into the RMSNorm backward), :func:`swiglu`,
 place into the logits buffer so no fp32 ``[tokens, 128256]`` tensor ever
 exists).  :class:`EvalAccumulator` is the evaluation side of the cross
 entropy: plain NLL and top-1 / top-k counts summed on the device.
+
+The generation ops at the end of the file (``csrc/kernels/decode.hip``) --
+:func:`rope_kv_append`, :func:`attention_decode`, :func:`sample` -- are
+inference only and also run on CPU tensors and unsupported shapes, through
+torch implementations of the same rules.
 """
 from __future__ import annotations
 
@@ -457,3 +462,244 @@ def linear_tw(x, w, wt, dw_kcontig: bool = False, tstash: TStash | None = None):
     weight gradient from transposed activations (``tstash``: the output
     gradient's transpose, if the next op's backward provides it)."""
     return _LinearTW.apply(x, w, wt, dw_kcontig, tstash)
+
+
+# ---------------------------------------------------------------- KV-cache generation
+# (csrc/kernels/decode.hip).  Each op runs its HIP kernel on bf16 HIP tensors
+# of a supported shape and a torch implementation of the same rules on CPU
+# tensors, other dtypes and unsupported shapes (``impl="torch"`` forces it).
+# Neither path syncs with the host: lengths, step and flags stay on the device.
+
+DECODE_KEY_TILE = 64
+
+
+def _rotate_half(x):
+    a, b = x.chunk(2, dim=-1)
+    return torch.cat((-b, a), dim=-1)
+
+
+def _hip_bf16(*ts) -> bool:
+    return all(t.is_cuda and t.dtype == torch.bfloat16 for t in ts)
+
+
+def _i32(t, name: str, n: int):
+    if t.dtype != torch.int32 or t.numel() != n or not t.is_contiguous():
+        raise ValueError(f"{name}: contiguous int32 tensor of {n} elements required")
+    return t
+
+
+def rope_kv_append(qkv, cos, sin, k_cache, v_cache, lens, n_heads: int, n_kv_heads: int, impl: str | None = None):
+    """Append the new token of every batch row to the KV cache.
+
+    ``qkv`` ``[B, (H + 2*Hkv)*D]`` is the fused QKV projection of ONE new
+    token per row, ``p = lens[b]`` (int32, device) its position, ``cos`` /
+    ``sin`` the fp32 tables of :func:`rope_tables`.  The ``H`` query heads are
+    rotated in place at position ``p``, the rotated K head and the V head are
+    written to ``k_cache[b, :, p]`` / ``v_cache[b, :, p]`` (caches are
+    ``[B, Hkv, max_len, D]``).  The arithmetic is :func:`rope_`'s, so the
+    appended key is bitwise the key prefill produces at that position.  A row
+    with ``p >= max_len`` or ``p`` at or past the table length is left alone
+    entirely.  Returns ``qkv``."""
+    B, Hkv, max_len, D = k_cache.shape
+    H = int(n_heads)
+    if Hkv != n_kv_heads or v_cache.shape != k_cache.shape:
+        raise ValueError("rope_kv_append: caches must both be [B, Hkv, max_len, D]")
+    if qkv.shape != (B, (H + 2 * Hkv) * D) or not qkv.is_contiguous():
+        raise ValueError(f"rope_kv_append: qkv must be contiguous [B, (H + 2*Hkv)*D], got {tuple(qkv.shape)}")
+    if cos.shape != sin.shape or cos.shape[-1] != D // 2:
+        raise ValueError("rope_kv_append: cos/sin must be [positions, D/2]")
+    _i32(lens, "rope_kv_append: lens", B)
+    if impl != "torch" and _hip_bf16(qkv, k_cache, v_cache) and D % 8 == 0 and k_cache.is_contiguous() \
+            and v_cache.is_contiguous():
+        cos, sin = cos.contiguous(), sin.contiguous()
+        if cos.dtype != torch.float32 or sin.dtype != torch.float32:
+            raise TypeError("rope_kv_append: fp32 cos/sin tables required")
+        _lib.check(_lib.lib().pto_rope_kv_append(qkv.data_ptr(), cos.data_ptr(), sin.data_ptr(), k_cache.data_ptr(),
+                                                 v_cache.data_ptr(), lens.data_ptr(), B, H, Hkv, D, max_len,
+                                                 cos.shape[0], _lib.stream_ptr(qkv.device)), "rope_kv_append")
+        return qkv
+    limit = min(max_len, cos.shape[0])
+    ok = ((lens >= 0) & (lens < limit))[:, None, None]
+    p = lens.clamp(0, limit - 1).long()
+    c = torch.cat([cos[p], cos[p]], -1)[:, None, :].float()
+    s = torch.cat([sin[p], sin[p]], -1)[:, None, :].float()
+    v3 = qkv.view(B, H + 2 * Hkv, D)
+    rot = v3[:, :H + Hkv].float()
+    rot = (rot * c + _rotate_half(rot) * s).to(qkv.dtype)
+    v3[:, :H] = torch.where(ok, rot[:, :H], v3[:, :H])
+    idx = p[:, None, None, None].expand(B, Hkv, 1, D)
+    for cache, new in ((k_cache, rot[:, H:]), (v_cache, v3[:, H + Hkv:])):
+        cache.scatter_(2, idx, torch.where(ok, new.to(cache.dtype), cache.gather(2, idx)[:, :, 0])[:, :, None])
+    return qkv
+
+
+def attention_decode_supported(H: int, Hkv: int, head_dim: int) -> bool:
+    """Shapes the split-KV decode kernel covers: head_dim 64 or 128 and a GQA
+    group ``H / Hkv`` of 1, 2, 4 or 8."""
+    return Hkv > 0 and H % Hkv == 0 and head_dim in (64, 128) and H // Hkv in (1, 2, 4, 8)
+
+
+def decode_splits(B: int, Hkv: int, max_len: int) -> int:
+    """Default split count of :func:`attention_decode`, from host integers
+    alone: about 512 ``(split, kv head, batch row)`` blocks for the 256 CUs,
+    but no split shorter than 256 keys.  Within 5 % of the best count of the
+    measured sweep at every shape of profiles/decode.md."""
+    by_len = -(-int(max_len) // 256)
+    by_cus = -(-512 // max(int(B) * int(Hkv), 1))
+    return max(1, min(by_len, by_cus))
+
+
+def decode_chunk(max_len: int, n_splits: int) -> int:
+    """Keys per split: ``ceil(max_len / n_splits)`` rounded up to the key tile."""
+    c = -(-int(max_len) // int(n_splits))
+    return -(-c // DECODE_KEY_TILE) * DECODE_KEY_TILE
+
+
+def attention_decode(q, k_cache, v_cache, lens, n_heads: int, n_kv_heads: int, n_splits: int | None = None,
+                     impl: str | None = None):
+    """One query row per head against the cached history: ``O [B, H*D]``.
+
+    ``q`` holds the (rotated) query heads of the new token in its first
+    ``H*D`` columns -- the fused QKV row ``[B, (H + 2*Hkv)*D]`` as it is, or
+    ``[B, H*D]``.  Row ``b`` attends to the keys ``[0, lens[b])`` of the
+    caches ``[B, Hkv, max_len, D]``; nothing past ``lens[b]`` is used, and
+    ``lens[b] == 0`` gives zeros.  ``n_splits`` (default
+    :func:`decode_splits`) workgroups share one head's history, each taking
+    :func:`decode_chunk` keys, and a second launch combines their partial
+    softmaxes in split order; the output bits depend on ``(inputs, lens,
+    max_len, n_splits)`` only.  ``impl="sdpa"`` / ``"torch"``, CPU tensors
+    and shapes outside :func:`attention_decode_supported` use torch's SDPA
+    over the valid prefix."""
+    B, Hkv, max_len, D = k_cache.shape
+    H = int(n_heads)
+    if Hkv != n_kv_heads or v_cache.shape != k_cache.shape or H % Hkv:
+        raise ValueError("attention_decode: caches must both be [B, Hkv, max_len, D] with H % Hkv == 0")
+    if q.dim() != 2 or q.shape[0] != B or q.shape[1] < H * D or q.stride(1) != 1:
+        raise ValueError(f"attention_decode: q must be [B, >= H*D] with unit inner stride, got {tuple(q.shape)}")
+    _i32(lens, "attention_decode: lens", B)
+    if n_splits is not None and (int(n_splits) != n_splits or n_splits < 1):
+        raise ValueError(f"attention_decode: n_splits must be an integer >= 1, got {n_splits}")
+    if impl not in (None, "hip", "sdpa", "torch"):
+        raise ValueError(f"attention_decode: impl must be hip|sdpa|torch, got {impl!r}")
+    if impl in (None, "hip") and _hip_bf16(q, k_cache, v_cache) and attention_decode_supported(H, Hkv, D) \
+            and k_cache.is_contiguous() and v_cache.is_contiguous():
+        if q.stride(0) % 8 or q.data_ptr() % 16:
+            q = q[:, :H * D].contiguous()
+        ns = decode_splits(B, Hkv, max_len) if n_splits is None else int(n_splits)
+        o = torch.empty(B, H * D, device=q.device, dtype=q.dtype)
+        ml = po = None
+        if ns > 1:
+            ml = torch.empty(B, H, ns, 2, device=q.device, dtype=torch.float32)
+            po = torch.empty(B, H, ns, D, device=q.device, dtype=torch.float32)
+        _lib.check(_lib.lib().pto_attn_decode(q.data_ptr(), q.stride(0), k_cache.data_ptr(), v_cache.data_ptr(),
+                                              lens.data_ptr(), o.data_ptr(), _p(ml), _p(po), B, H, Hkv, D, max_len, ns,
+                                              D ** -0.5, _lib.stream_ptr(q.device)), "attn_decode")
+        return o
+    valid = (torch.arange(max_len, device=q.device)[None, :] < lens[:, None])[:, None, :, None]  # [B, 1, max_len, 1]
+    zero = torch.zeros((), device=q.device, dtype=k_cache.dtype)
+    k = torch.where(valid, k_cache, zero)  # whatever the tail holds is discarded, never multiplied
+    v = torch.where(valid, v_cache, zero)
+    q4 = q[:, :H * D].reshape(B, H, 1, D)
+    o = torch.nn.functional.scaled_dot_product_attention(q4, k.to(q.dtype), v.to(q.dtype),
+                                                         attn_mask=valid.transpose(2, 3), enable_gqa=Hkv != H)
+    o = torch.where((lens > 0)[:, None, None, None], o, torch.zeros((), device=q.device, dtype=o.dtype))
+    return o.reshape(B, H * D)
+
+
+def _sample_torch(z, u, temperature: float, top_k: int):
+    """The sampler's rules on torch ops (fp64 CDF): ``z`` [B, V], ``u`` [B]."""
+    zf = z.float()
+    if temperature <= 0:
+        return zf.argmax(-1)  # the first of equal maxima
+    V = zf.shape[-1]
+    if 0 < top_k < V:
+        kept = zf >= zf.topk(top_k, dim=-1).values[:, -1:]  # ties at the k-th largest value are all kept
+    else:
+        kept = torch.ones_like(zf, dtype=torch.bool)
+    zd = zf.double()
+    w = torch.where(kept, torch.exp((zd - zd.max(-1, keepdim=True).values) / temperature), torch.zeros_like(zd))
+    cdf = w.cumsum(-1)
+    hit = kept & (cdf > u.double()[:, None] * cdf[:, -1:])
+    first = hit.int().argmax(-1)  # first kept index whose running sum exceeds u * total
+    last = V - 1 - kept.flip(-1).int().argmax(-1)
+    return torch.where(hit.any(-1), first, last)
+
+
+def sample(logits, u=None, temperature: float = 0.0, top_k: int = 0, cur=None, out=None, step=None, done=None,
+           eos_id: int | None = None, lens=None, advance: bool = False, impl: str | None = None):
+    """Pick one token per row of ``logits`` ``[B, V]``; returns ``cur`` ``[B]`` int64.
+
+    * ``temperature == 0``: argmax, the first index among equal maxima.
+    * ``temperature > 0``: a draw from ``softmax(z / T)`` over the kept set by
+      inverse CDF in index order: the first kept index whose running sum of
+      probabilities exceeds ``u[step, b]``.  ``u`` is ``[n_steps, B]`` fp32
+      uniforms (``[B]`` counts as one step).
+    * ``top_k > 0`` keeps every logit ``>=`` the k-th largest value, ties
+      included.  No top-p.
+
+    Bookkeeping, all on the device: with ``st = step[0]`` (int32 ``[1]``; 0
+    without ``step``) the token is written to ``cur[b]`` and ``out[b, st]``
+    (int64 ``[B, n_steps]``); a row whose ``done[b]`` (int32) is set emits
+    ``eos_id``, a row that emits ``eos_id`` sets it; ``advance`` then adds 1
+    to ``step[0]`` and to every ``lens[b]`` (either may be None).
+
+    bf16 HIP logits with ``V % 8 == 0`` run ``k_sample`` (no scalar tail: the
+    kernel refuses other widths, as ``k_ce_eval`` does); everything else runs
+    the same rules on torch ops."""
+    if logits.dim() != 2:
+        raise ValueError(f"sample: logits must be [B, V], got {tuple(logits.shape)}")
+    B, V = logits.shape
+    temperature, top_k = float(temperature), int(top_k)
+    if not temperature >= 0.0 or top_k < 0:
+        raise ValueError(f"sample: temperature and top_k must be >= 0, got {temperature}, {top_k}")
+    dev = logits.device
+    if temperature > 0:
+        if u is None:
+            raise ValueError("sample: temperature > 0 needs the uniforms u")
+        u = u.reshape(-1, B)
+        if u.dtype != torch.float32 or not u.is_contiguous():
+            raise TypeError("sample: u must be contiguous fp32")
+    n_steps = out.shape[1] if out is not None else (u.shape[0] if u is not None and u.dim() == 2 else 1)
+    if u is not None and temperature > 0 and u.shape[0] != n_steps:
+        raise ValueError(f"sample: u has {u.shape[0]} steps, out has {n_steps}")
+    if cur is None:
+        cur = torch.empty(B, device=dev, dtype=torch.int64)
+    for t, name, shape in ((cur, "cur", (B,)), (out, "out", (B, n_steps))):
+        if t is not None and (t.dtype != torch.int64 or tuple(t.shape) != shape or not t.is_contiguous()):
+            raise ValueError(f"sample: {name} must be contiguous int64 {shape}")
+    if step is not None:
+        _i32(step, "sample: step", 1)
+    if done is not None:
+        _i32(done, "sample: done", B)
+    if lens is not None:
+        _i32(lens, "sample: lens", B)
+    eos = -1 if eos_id is None else int(eos_id)
+    if impl != "torch" and _hip_bf16(logits) and V % 8 == 0 and V >= 8:
+        logits = logits.contiguous()
+        if logits.data_ptr() % 16:
+            logits = logits.clone()
+        _lib.check(_lib.lib().pto_sample(logits.data_ptr(), _p(u) if temperature > 0 else None, cur.data_ptr(),
+                                         _p(out), n_steps, _p(step), _p(done), B, V, temperature, top_k, eos,
+                                         1 if advance else 0, _p(lens), _lib.stream_ptr(dev)), "sample")
+        return cur
+    st = None if step is None else step.long().clamp(0, n_steps - 1)  # [1], on the device
+    urow = None
+    if temperature > 0:
+        urow = u[0] if st is None else u.index_select(0, st)[0]
+    tok = _sample_torch(logits, urow, temperature, top_k)
+    if done is not None:
+        tok = torch.where(done != 0, torch.full_like(tok, eos), tok)
+        if eos >= 0:
+            done.copy_(((done != 0) | (tok == eos)).to(done.dtype))
+    cur.copy_(tok)
+    if out is not None:
+        col = torch.zeros(1, device=dev, dtype=torch.int64) if st is None else st
+        inside = torch.ones(1, device=dev, dtype=torch.bool) if step is None else (step >= 0) & (step < n_steps)
+        idx = col.expand(B)[:, None]
+        out.scatter_(1, idx, torch.where(inside, tok, out.gather(1, idx)[:, 0])[:, None])
+    if advance:
+        if step is not None:
+            step += 1
+        if lens is not None:
+            lens += 1
+    return cur

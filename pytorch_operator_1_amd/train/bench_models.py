@@ -425,6 +425,19 @@ class LlamaTrainer(CheckpointMixin):
         """The dict of the last :meth:`evaluate`; None before the first."""
         return self._eval
 
+    def sample(self, prompt_len: int = 16, new_tokens: int = 32, temperature: float = 0.0, top_k: int = 0,
+               seed: int = 0):
+        """Generate ``new_tokens`` tokens (:meth:`..models.llama.Llama.generate`)
+        after the first ``prompt_len`` tokens of held-out batch 0, row 0:
+        ``(prompt, tokens)`` as Python lists (the one host sync).  Like
+        :meth:`evaluate` it writes nothing training reads."""
+        if not 1 <= int(prompt_len) <= self.seq_len:
+            raise ValueError(f"sample: prompt_len must be in [1, {self.seq_len}], got {prompt_len}")
+        prompt = self._heldout_batches(1)[0][0][:1, :int(prompt_len)].contiguous()
+        out = self.model.generate(prompt, max_new_tokens=int(new_tokens), temperature=temperature, top_k=top_k,
+                                  seed=seed)
+        return prompt[0].tolist(), out[0].tolist()
+
     def last_grad_norm(self):
         return _scalar(self.opt.grad_norm) if self.max_grad_norm is not None else None
 

@@ -28,6 +28,13 @@ but a restarted replica starts from step 0.  Here:
   chunks of ``--eval-head-chunk R`` rows so the full logits never exist.
   It prints an ``eval step`` line, emits an ``eval`` metrics event, and its
   time stays out of the samples/s of the training log;
+* ``--sample-interval N`` (Llama only) lets rank 0 generate
+  ``--sample-tokens T`` tokens after the first ``--sample-prompt-len P``
+  tokens of a held-out row every N optimizer steps and after the last one,
+  with the KV-cache decode path (greedy, or ``--temperature F`` /
+  ``--top-k K`` sampling from ``--sample-seed S``).  It prints a
+  ``sample step`` line, emits a ``sample`` metrics event, and its time
+  stays out of the samples/s as well;
 * a collective failure exits 138 (retryable for ``restartPolicy: ExitCode``)
   exactly like the MNIST trainer, so kill/rejoin works for these models too.
 
@@ -54,7 +61,7 @@ from .mnist import Metrics, run_with_retryable_exit
 def parse_args(argv=None):
     p = argparse.ArgumentParser(description="Llama-3 / ResNet-50 DDP trainer (MI355X)")
     p.add_argument("--model", default="llama3-tiny",
-                   choices=["llama3-tiny", "llama3-1b", "llama3-8b", "resnet50"])
+                   choices=["llama3-tiny", "llama3-mini", "llama3-1b", "llama3-8b", "resnet50"])
     p.add_argument("--steps", type=int, default=100)
     p.add_argument("--batch-size", type=int, default=None, help="per rank (default 2 llama, 64 resnet50)")
     p.add_argument("--seq-len", type=int, default=512)
@@ -90,7 +97,27 @@ def parse_args(argv=None):
     p.add_argument("--eval-topk", type=int, default=5, help="k of the top-k accuracy")
     p.add_argument("--eval-head-chunk", type=int, default=2048,
                    help="rows of logits alive at once during evaluation (the head GEMM runs per chunk)")
+    p.add_argument("--sample-interval", type=int, default=0,
+                   help="generate from a held-out prompt with the Llama model every N optimizer steps and after "
+                        "the last one (default 0: off)")
+    p.add_argument("--sample-tokens", type=int, default=32, help="tokens to generate per sample")
+    p.add_argument("--sample-prompt-len", type=int, default=16, help="prompt tokens taken from the held-out row")
+    p.add_argument("--temperature", type=float, default=0.0, help="sampling temperature (default 0: greedy)")
+    p.add_argument("--top-k", type=int, default=0, help="sample among the k most likely tokens (default 0: all)")
+    p.add_argument("--sample-seed", type=int, default=0, help="seed of the sampler's uniforms")
     args = p.parse_args(argv)
+    if args.sample_interval < 0:
+        p.error("--sample-interval must be >= 0")
+    if args.sample_tokens < 1 or args.sample_prompt_len < 1:
+        p.error("--sample-tokens and --sample-prompt-len must be >= 1")
+    if not args.temperature >= 0.0 or args.top_k < 0:
+        p.error("--temperature and --top-k must be >= 0")
+    if args.model == "resnet50" and (args.sample_interval or args.sample_tokens != 32 or args.sample_prompt_len != 16
+                                     or args.temperature != 0.0 or args.top_k != 0 or args.sample_seed != 0):
+        p.error("--sample-interval / --sample-tokens / --sample-prompt-len / --temperature / --top-k / "
+                "--sample-seed are for the Llama models")
+    if args.model != "resnet50" and args.sample_interval and args.sample_prompt_len > args.seq_len:
+        p.error("--sample-prompt-len must not exceed --seq-len")
     if args.eval_interval < 0:
         p.error("--eval-interval must be >= 0")
     if args.eval_batches < 1 or args.eval_topk < 1 or args.eval_head_chunk < 1:
@@ -138,6 +165,21 @@ def _evaluate(args, trainer, device, metrics, done: int, rank: int) -> float:
           f"top{ev['k']}={ev['topk']:.6f}\ttokens={ev['tokens']}", flush=True)
     metrics.emit(event="eval", step=done, loss=ev["loss"], ppl=ev["ppl"], top1=ev["top1"], topk=ev["topk"],
                  k=ev["k"], tokens=ev["tokens"], rank=rank)
+    return time.time() - t0
+
+
+def _sample(args, trainer, device, metrics, done: int, rank: int) -> float:
+    """One generation after optimizer step ``done``, on rank 0 alone (it
+    needs no collective): print and emit it, return the seconds it took."""
+    if device.type == "cuda":
+        torch.cuda.synchronize(device)
+    t0 = time.time()
+    if rank == 0:
+        prompt, tokens = trainer.sample(prompt_len=args.sample_prompt_len, new_tokens=args.sample_tokens,
+                                        temperature=args.temperature, top_k=args.top_k, seed=args.sample_seed)
+        print(f"sample step {done}\tprompt={prompt}\ttokens={tokens}", flush=True)
+        metrics.emit(event="sample", step=done, prompt=prompt, tokens=tokens, temperature=args.temperature,
+                     top_k=args.top_k, seed=args.sample_seed, rank=rank)
     return time.time() - t0
 
 
@@ -192,6 +234,8 @@ def _main(argv=None):
             t_last, steps_since = now, 0
         if args.eval_interval and (done % args.eval_interval == 0 or done == args.steps):
             t_last += _evaluate(args, trainer, device, metrics, done, rank)  # outside the throughput window
+        if args.sample_interval and (done % args.sample_interval == 0 or done == args.steps):
+            t_last += _sample(args, trainer, device, metrics, done, rank)
         if saver and args.checkpoint_interval and done % args.checkpoint_interval == 0 and done < args.steps:
             saver.save(done, trainer.checkpoint_tensors(), trainer.checkpoint_meta())
     if saver:

@@ -27,7 +27,10 @@ large-model DDP config, built MI355X-first:
   :meth:`Llama.decode_step` and :meth:`Llama.generate` -- one new token per
   row against cached K/V, on the kernels of ``csrc/kernels/decode.hip``
   (cache append, split-KV decode attention, sampler), every length and
-  counter on the device so a step replays from a captured graph.
+  counter on the device so a step replays from a captured graph.  Under
+  ``PTO_SKINNY=1`` the step's linear layers (``M = B <= 16``) run on the
+  package's skinny MFMA GEMM (``csrc/kernels/gemm_skinny.hip``), SwiGLU
+  folded into ``w13``'s epilogue, instead of hipBLASLt.
 
 ``impl="torch"`` is a plain PyTorch implementation of the same math used as
 the numerics reference (and for CPU tests).
@@ -183,12 +186,13 @@ class LlamaBlock(nn.Module):
                 y = llm.rmsnorm(h, self.attn_norm, c.norm_eps)
             else:
                 h, y = llm.add_rmsnorm(h, delta, self.attn_norm, c.norm_eps)
-            qkv = _lin(y, self.wqkv)
+            qkv = _lin_decode(y, self.wqkv.weight)
             llm.rope_kv_append(qkv, rope[0], rope[1], k, v, cache.lens, c.n_heads, c.n_kv_heads)
             ctx = llm.attention_decode(qkv, k, v, cache.lens_incl, c.n_heads, c.n_kv_heads,
                                        impl="sdpa" if ATTN_IMPL == "sdpa" else None)
-            h, y = llm.add_rmsnorm(h, _lin(ctx, self.wo), self.ffn_norm, c.norm_eps)
-            return h, _lin(llm.swiglu(_lin(y, self.w13)), self.w2)
+            h, y = llm.add_rmsnorm(h, _lin_decode(ctx, self.wo.weight), self.ffn_norm, c.norm_eps)
+            # on the skinny kernel the SwiGLU is w13's epilogue: no [B, 2F] round trip
+            return h, _lin_decode(_lin_decode(y, self.w13.weight, swiglu=True), self.w2.weight)
         if delta is not None:
             h = h + delta
         y = _rmsnorm_ref(h, self.attn_norm, c.norm_eps)
@@ -234,6 +238,15 @@ def _lin(x, mod: nn.Linear, tstash=None):
     # each GEMM on the package's kernel or on the library (PTO_GEMM); all on
     # the library, it is F.linear / llm.linear_tw itself
     return gemm.linear(x, mod.weight, getattr(mod, "weight_t", None), getattr(mod, "dw_kcontig", False), tstash)
+
+
+def _lin_decode(x, w, swiglu: bool = False):
+    """A linear layer of the decode step (``x [B, k_in]``): the skinny GEMM
+    under ``PTO_SKINNY`` (:func:`..ops.gemm.skinny_plan`), else :func:`_lin`'s
+    calls (and ``llm.swiglu``)."""
+    from ..ops import gemm
+
+    return gemm.linear_decode(x, w, swiglu)
 
 
 def _plan(kind: str, x, mod: nn.Linear) -> str:
@@ -360,7 +373,18 @@ class Llama(nn.Module):
             return llm.add_rmsnorm(h, delta, self.norm, self.cfg.norm_eps)[1]
         return _rmsnorm_ref(h + delta, self.norm, self.cfg.norm_eps)
 
-    def _head(self, y):
+    def _head(self, y, decode: bool = False):
+        """The head GEMM; ``decode``: ``y`` is one row per sequence (a decode
+        step, the last positions of a prefill), which may take the skinny
+        kernel -- with the tied embedding too."""
+        if decode and self.impl == "hip" and y.is_cuda:
+            from ..ops import gemm
+
+            w = self._head_weight()
+            # the tied embedding leaves F.linear only for the skinny kernel
+            if self.lm_head is not None or (y.dtype == w.dtype == torch.bfloat16 and
+                                            gemm.skinny_plan(y.shape[0], w.shape[0], w.shape[1]) == "hip"):
+                return _lin_decode(y, w)
         if self.impl == "hip" and self.lm_head is not None:
             return _lin(y, self.lm_head)
         return F.linear(y, self._head_weight())
@@ -408,7 +432,7 @@ class Llama(nn.Module):
         cache.reset()
         cache.lens.copy_(lens)
         last = (lens.long() - 1).clamp(0, P - 1)[:, None, None].expand(B, 1, c.dim)
-        return self._head(y.view(B, P, c.dim).gather(1, last)[:, 0].contiguous())
+        return self._head(y.view(B, P, c.dim).gather(1, last)[:, 0].contiguous(), decode=True)
 
     @torch.no_grad()
     def decode_step(self, cur: torch.Tensor, cache: KVCache):
@@ -431,7 +455,7 @@ class Llama(nn.Module):
             y = llm.add_rmsnorm(h, delta, self.norm, self.cfg.norm_eps)[1]
         else:
             y = _rmsnorm_ref(h + delta, self.norm, self.cfg.norm_eps)
-        return self._head(y)
+        return self._head(y, decode=True)
 
     @torch.no_grad()
     def generate(self, prompts: torch.Tensor, prompt_lens=None, max_new_tokens: int = 16, temperature: float = 0.0,

@@ -233,3 +233,128 @@ def linear(x, w, wt=None, dw_kcontig: bool = False, tstash=None):
     from . import llm
 
     return llm.linear_tw(x, w, wt, dw_kcontig, tstash)
+
+
+# ---------------------------------------------------------------- skinny GEMM (decode)
+# csrc/kernels/gemm_skinny.hip: y[M,N] = x[M,K] W[N,K]^T for 1 <= M <= 16, the
+# linear layers of a decode step, optionally with the SwiGLU of a fused
+# gate|up weight in the epilogue.
+
+# (n_out, k_in) of the linear layers whose decode-time product goes to the
+# skinny kernel under PTO_SKINNY=auto.  Empty: generation's default bits stay
+# what the library gives; profiles/decode_linear.md lists the candidates.
+SKINNY_AUTO: frozenset = frozenset()
+
+SKINNY_MAX_ROWS = 16
+_skinny_ws: dict = {}  # device -> uint8 workspace for the split-K partials
+
+
+def skinny_takes(rows: int, n_out: int, k_in: int, swiglu: bool = False) -> bool:
+    """The skinny kernel's shape rules for a linear layer ``[n_out, k_in]`` on
+    ``rows`` tokens (contiguous operands): 1..16 rows, output rows of the
+    weight a multiple of 16 (of 32 with ``swiglu``: ``F = n_out / 2`` a
+    multiple of 16), contraction a multiple of 32."""
+    if not 1 <= rows <= SKINNY_MAX_ROWS or n_out < 1 or k_in < 1:
+        return False
+    return n_out % (32 if swiglu else 16) == 0 and k_in % 32 == 0
+
+
+def skinny_plan(rows: int, n_out: int, k_in: int) -> str:
+    """``"hip"`` (the skinny kernel) or ``"lib"`` (hipBLASLt through torch)
+    for the decode-time product of a linear layer ``[n_out, k_in]`` with
+    ``rows`` tokens, under the ``PTO_SKINNY`` switch (read at call time)."""
+    mode = os.environ.get("PTO_SKINNY", "auto")
+    if mode not in ("auto", "0", "1"):
+        raise ValueError(f"PTO_SKINNY must be auto, 0 or 1, not {mode!r}")
+    takes = skinny_takes(rows, n_out, k_in)
+    if takes and (mode == "1" or (mode == "auto" and (n_out, k_in) in SKINNY_AUTO)):
+        return "hip"
+    return "lib"
+
+
+def skinny_splits(n_out: int, k_in: int) -> int:
+    """The kernel's default K split across workgroups: a function of the
+    layer shape alone, never of the row count."""
+    return int(_lib.lib().pto_gemm_skinny_splits(n_out, k_in))
+
+
+def _skinny_workspace(device, nbytes: int) -> torch.Tensor:
+    ws = _skinny_ws.get(device)
+    if ws is None or ws.numel() < nbytes:
+        ws = _skinny_ws[device] = torch.empty(max(nbytes, 1 << 20), device=device, dtype=torch.uint8)
+    return ws
+
+
+def skinny_nt(x, w, out=None, out_dtype=None, swiglu: bool = False, n_splits: int | None = None):
+    """``x[M,K] @ w[N,K].T`` for ``1 <= M <= 16`` (bf16 in, fp32 sums, bf16
+    or fp32 out).  ``swiglu``: ``w`` is a fused gate|up weight ``[2F, K]`` and
+    the result is ``silu(g) * u`` as bf16 ``[M, F]``, bitwise
+    :func:`..ops.llm.swiglu` of the plain bf16 result with the same
+    ``n_splits`` (default :func:`skinny_splits`).  Row ``m`` of the result
+    depends on ``x[m]``, ``w`` and ``n_splits`` only.  HIP tensors launch the
+    kernel and raise on a refused shape; CPU tensors compute the same with
+    torch."""
+    M, N, K, _ = _dims(NT, x, w)
+    if swiglu and N % 2:
+        raise ValueError(f"skinny_nt: swiglu needs an even number of weight rows, got {N}")
+    oshape = (M, N // 2) if swiglu else (M, N)
+    if out is not None:
+        if tuple(out.shape) != oshape or out.device != x.device:
+            raise ValueError(f"skinny_nt: out must be {oshape} on {x.device}")
+        if out_dtype is not None and out_dtype != out.dtype:
+            raise ValueError(f"skinny_nt: out_dtype {out_dtype} != out.dtype {out.dtype}")
+        out_dtype = out.dtype
+    if not x.is_cuda:
+        r = x.mm(w.t())
+        if swiglu:
+            g, u = r.float().chunk(2, dim=-1)
+            r = (g * torch.sigmoid(g)).to(x.dtype).float() * u
+        r = r.to(out_dtype or x.dtype)
+        if out is None:
+            return r
+        out.copy_(r)
+        return out
+    if x.dtype != torch.bfloat16 or w.dtype != torch.bfloat16 or w.device != x.device:
+        raise TypeError(f"skinny_nt: bf16 operands on one HIP device required (got {x.dtype}, {w.dtype})")
+    out_dtype = out_dtype or torch.bfloat16
+    if out_dtype not in (torch.bfloat16, torch.float32) or (swiglu and out_dtype != torch.bfloat16):
+        raise TypeError(f"skinny_nt: output must be bf16{'' if swiglu else ' or fp32'}, not {out_dtype}")
+    if out is None:
+        out = torch.empty(oshape, device=x.device, dtype=out_dtype)
+    for t, what in ((x, "x"), (w, "w"), (out, "out")):
+        if t.stride(1) != 1:
+            raise RuntimeError(f"skinny_nt: {what} must have unit inner stride (strides {t.stride()})")
+    lda, ldb, ldc = (t.stride(0) if t.shape[0] > 1 else t.shape[1] for t in (x, w, out))
+    L = _lib.lib()
+    ns = int(L.pto_gemm_skinny_splits(N, K)) if n_splits is None else int(n_splits)
+    nbytes = L.pto_gemm_skinny_workspace(M, N, ns) if ns > 1 else 0
+    ws = _skinny_workspace(x.device, nbytes) if nbytes > 0 else None
+    rc = L.pto_gemm_skinny(x.data_ptr(), lda, w.data_ptr(), ldb, out.data_ptr(), ldc, int(out_dtype == torch.float32),
+                           int(bool(swiglu)), M, N, K, ns, _lib.ptr(ws), nbytes if ws is not None else 0,
+                           _lib.stream_ptr(x.device))
+    if rc == -1:
+        raise RuntimeError(f"skinny_nt: unsupported shape or layout: x {tuple(x.shape)} strides {x.stride()}, "
+                           f"w {tuple(w.shape)} strides {w.stride()}, out strides {out.stride()}, n_splits {ns} "
+                           "(1..16 rows, weight rows a multiple of 16 (32 with swiglu), contraction a multiple of "
+                           "32, row strides multiples of 8, 16-byte aligned pointers, 1..64 splits)")
+    _lib.check(rc, "skinny_nt")
+    return out
+
+
+def linear_decode(x, w, swiglu: bool = False):
+    """The bias-free linear layer of a decode step, ``x [B, k_in]`` against
+    ``w [n_out, k_in]``, with ``swiglu`` the SwiGLU of a fused gate|up weight
+    applied to it.  bf16 HIP tensors under a ``"hip"`` :func:`skinny_plan`
+    take :func:`skinny_nt` (one launch, no ``[B, 2F]`` intermediate);
+    everything else makes the calls of :func:`linear` and
+    :func:`..ops.llm.swiglu`."""
+    if x.is_cuda and x.dim() == 2 and x.dtype == torch.bfloat16 and w.dtype == torch.bfloat16 \
+            and skinny_takes(x.shape[0], w.shape[0], w.shape[1], swiglu) \
+            and skinny_plan(x.shape[0], w.shape[0], w.shape[1]) == "hip":
+        return skinny_nt(_rows(x), w, swiglu=swiglu)
+    y = linear(x, w)
+    if swiglu:
+        from . import llm
+
+        y = llm.swiglu(y)
+    return y

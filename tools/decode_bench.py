@@ -15,13 +15,22 @@ back-to-back calls, median and min over ``--rounds``; bytes/s counts the K
 and V bytes of the valid history once (2 * B * Hkv * len * D * 2 B).
 
 ``--part generate``: ``Llama.generate`` tokens/s, ``--new`` tokens after a
-``--prompt``-token prompt, B in {1, 8}, eager against ``graph=True``; host
-clock around a call that ends in a device synchronise, the prefill (a call
-with one new token) timed the same way and subtracted for the decode rate.
+``--prompt``-token prompt, B in {1, 8}, eager against ``graph=True``, each
+with ``PTO_SKINNY`` 0 and 1 (the decode linears on hipBLASLt or on the
+package's skinny GEMM); host clock around a call that ends in a device
+synchronise, the prefill (a call with one new token) timed the same way and
+subtracted for the decode rate.
+
+``--part linear``: every linear layer shape of ``--models`` at M in {1, 8,
+16}: ``ops.gemm.skinny_nt`` against ``F.linear``, and for the gate|up weight
+the SwiGLU-fused call against ``F.linear`` + ``llm.swiglu``.  Each call reads
+the next of several weight copies (at least 768 MB in rotation); the two
+sides alternate round by round in one process; bytes/s counts the weight
+bytes once.  Then a sweep of ``n_splits`` for the ``wo`` / ``w2`` shapes.
 
 One JSON line per row.
 
-    python tools/decode_bench.py [--part attn|generate|all] [--rounds 15] [--reps 20]
+    python tools/decode_bench.py [--part attn|generate|linear|all] [--rounds 15] [--reps 20]
                                  [--models llama3-1b] [--prompt 512] [--new 128] [--repeats 3]
 """
 from __future__ import annotations
@@ -123,6 +132,85 @@ def attn(args):
             torch.cuda.empty_cache()
 
 
+def timed_pair(fns, rounds: int, reps: int):
+    """``timed`` for several callables measured alternately, round by round:
+    a list of (median, min) microseconds per call."""
+    import torch
+
+    for fn in fns:
+        for _ in range(reps):
+            fn()
+    ts = [[] for _ in fns]
+    for _ in range(rounds):
+        for i, fn in enumerate(fns):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            for _ in range(reps):
+                fn()
+            b.record()
+            b.synchronize()
+            ts[i].append(a.elapsed_time(b) * 1e3 / reps)
+    return [(sorted(t)[len(t) // 2], min(t)) for t in ts]
+
+
+def linear_shapes(cfg):
+    """(layer, n_out, k_in) of the decode step's linear layers."""
+    qkv = (cfg.n_heads + 2 * cfg.n_kv_heads) * cfg.head_dim
+    return [("wqkv", qkv, cfg.dim), ("wo", cfg.dim, cfg.n_heads * cfg.head_dim), ("w13", 2 * cfg.ffn_dim, cfg.dim),
+            ("w2", cfg.dim, cfg.ffn_dim), ("head", cfg.vocab_size, cfg.dim)]
+
+
+def linear(args):
+    import torch
+    import torch.nn.functional as F
+
+    from pytorch_operator_1_amd.models.llama import CONFIGS
+    from pytorch_operator_1_amd.ops import gemm, llm
+
+    dev = torch.device("cuda")
+    for name in args.models.split(","):
+        for layer, n_out, k_in in linear_shapes(CONFIGS[name]):
+            w_bytes = n_out * k_in * 2
+            ncopy = max(2, -(-LLC_BYTES // w_bytes))
+            g = torch.Generator(device=dev).manual_seed(0)
+            ws = [torch.randn(n_out, k_in, device=dev, dtype=torch.bfloat16, generator=g) * k_in ** -0.5
+                  for _ in range(ncopy)]
+            turn = [0]
+
+            def nxt():
+                turn[0] = (turn[0] + 1) % ncopy
+                return ws[turn[0]]
+
+            def row(case, med, mn, **kw):
+                print(json.dumps({"model": name, "layer": layer, "n_out": n_out, "k_in": k_in, **kw, "case": case,
+                                  "weight_MB": round(w_bytes / 2**20, 1), "weight_copies": ncopy,
+                                  "rounds": args.rounds, "reps": args.reps, "median_us": round(med, 2),
+                                  "min_us": round(mn, 2), "TBps_median": round(w_bytes / med / 1e6, 3),
+                                  "fraction_of_ceiling": round(w_bytes / (med * 1e-6) / CEILING, 3)}), flush=True)
+
+            for M in (1, 8, 16):
+                x = torch.randn(M, k_in, device=dev, dtype=torch.bfloat16, generator=g)
+                ns = gemm.skinny_splits(n_out, k_in)
+                err = float((gemm.skinny_nt(x, ws[0]).float() - F.linear(x, ws[0]).float()).norm() /
+                            F.linear(x, ws[0]).float().norm())
+                sides = [("skinny_nt", lambda: gemm.skinny_nt(x, nxt())), ("F.linear", lambda: F.linear(x, nxt()))]
+                if layer == "w13":
+                    sides += [("skinny_nt swiglu", lambda: gemm.skinny_nt(x, nxt(), swiglu=True)),
+                              ("F.linear + llm.swiglu", lambda: llm.swiglu(F.linear(x, nxt())))]
+                for (case, _), (med, mn) in zip(sides, timed_pair([f for _, f in sides], args.rounds, args.reps)):
+                    row(case, med, mn, M=M, n_splits=ns if case.startswith("skinny") else None,
+                        relerr_vs_lib=round(err, 5))
+            if layer in ("wo", "w2"):
+                x = torch.randn(1, k_in, device=dev, dtype=torch.bfloat16, generator=g)
+                sweep = [1, 2, 4, 8, 16, 32]
+                res = timed_pair([lambda n=n: gemm.skinny_nt(x, nxt(), n_splits=n) for n in sweep], args.rounds,
+                                 args.reps)
+                for n, (med, mn) in zip(sweep, res):
+                    row("skinny_nt, n_splits sweep", med, mn, M=1, n_splits=n)
+            del ws
+            torch.cuda.empty_cache()
+
+
 def generate(args):
     import torch
 
@@ -136,42 +224,55 @@ def generate(args):
             prompts = torch.randint(0, model.cfg.vocab_size, (B, args.prompt), device=dev,
                                     generator=torch.Generator(device=dev).manual_seed(1))
 
-            def run(n_new, graph):
+            def run_once(n_new, graph):
                 torch.cuda.synchronize()
                 t0 = time.perf_counter()
                 out = model.generate(prompts, max_new_tokens=n_new, graph=graph)
                 torch.cuda.synchronize()
                 return time.perf_counter() - t0, out
 
+            def run(n_new, graph, skinny="0"):
+                os.environ["PTO_SKINNY"] = skinny  # read at call time by ops.gemm.skinny_plan
+                try:
+                    return run_once(n_new, graph)
+                finally:
+                    os.environ.pop("PTO_SKINNY", None)
+
             outs = {}
-            for graph in (False, True):  # warm every path: code objects, the library's picks, the rope tables
-                run(args.new, graph)
-            run(1, False)
-            t = {"prefill": [], False: [], True: []}
+            keys = [(graph, skinny) for skinny in ("0", "1") for graph in (False, True)]
+            for graph, skinny in keys:  # warm every path: code objects, the library's picks, the rope tables
+                run(args.new, graph, skinny)
+            t = {"prefill0": [], "prefill1": [], **{k: [] for k in keys}}
+            for skinny in ("0", "1"):
+                run(1, False, skinny)
             for _ in range(args.repeats):
-                t["prefill"].append(run(1, False)[0])
-                for graph in (False, True):
-                    dt, outs[graph] = run(args.new, graph)
-                    t[graph].append(dt)
-            pre = sorted(t["prefill"])[len(t["prefill"]) // 2]
-            for graph in (False, True):
-                ts = sorted(t[graph])
+                for skinny in ("0", "1"):
+                    t["prefill" + skinny].append(run(1, False, skinny)[0])
+                for graph, skinny in keys:
+                    dt, outs[graph, skinny] = run(args.new, graph, skinny)
+                    t[graph, skinny].append(dt)
+            for graph, skinny in keys:
+                pre = sorted(t["prefill" + skinny])[len(t["prefill" + skinny]) // 2]
+                ts = sorted(t[graph, skinny])
                 med = ts[len(ts) // 2]
-                print(json.dumps({"case": "generate graph" if graph else "generate eager", "model": name, "B": B,
+                print(json.dumps({"case": "generate graph" if graph else "generate eager", "PTO_SKINNY": int(skinny),
+                                  "model": name, "B": B,
                                   "prompt": args.prompt, "new_tokens": args.new, "repeats": args.repeats,
                                   "median_ms": round(med * 1e3, 2), "min_ms": round(ts[0] * 1e3, 2),
                                   "prefill_ms": round(pre * 1e3, 2),
                                   "decode_ms_per_step": round((med - pre) / (args.new - 1) * 1e3, 4),
                                   "decode_tokens_per_s": round(B * (args.new - 1) / (med - pre), 1),
                                   "tokens_per_s_with_prefill": round(B * args.new / med, 1),
-                                  "graph_equals_eager": bool(torch.equal(outs[False], outs[True]))}), flush=True)
+                                  "graph_equals_eager": bool(torch.equal(outs[False, skinny], outs[True, skinny])),
+                                  "tokens_equal_PTO_SKINNY_0": bool(torch.equal(outs[graph, skinny],
+                                                                                outs[graph, "0"]))}), flush=True)
         del model
         torch.cuda.empty_cache()
 
 
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--part", choices=["attn", "generate", "all"], default="all")
+    ap.add_argument("--part", choices=["attn", "generate", "linear", "all"], default="all")
     ap.add_argument("--rounds", type=int, default=15)
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--models", default="llama3-1b")
@@ -187,6 +288,8 @@ def main():
         sys.exit("decode_bench: needs a HIP device (no CPU fallback: a CPU timing says nothing here)")
     if args.part in ("attn", "all"):
         attn(args)
+    if args.part in ("linear", "all"):
+        linear(args)
     if args.part in ("generate", "all"):
         generate(args)
 

@@ -31,6 +31,12 @@ large-model DDP config, built MI355X-first:
   ``PTO_SKINNY=1`` the step's linear layers (``M = B <= 16``) run on the
   package's skinny MFMA GEMM (``csrc/kernels/gemm_skinny.hip``), SwiGLU
   folded into ``w13``'s epilogue, instead of hipBLASLt.
+* Multi-token extend: :meth:`Llama.extend` feeds ``T`` tokens per row to a
+  cache that already holds history -- one pass over the weights, the
+  ``T * H`` query rows on the MFMA kernel of ``csrc/kernels/attn_extend.hip``
+  (head_dim 64 and 128, any ``T``).  ``prefill(chunk=c)`` /
+  ``generate(prefill_chunk=c)`` build the cache ``c`` positions at a time on
+  it; ``extend(logits="all")`` is what a speculative-decoding verifier needs.
 
 ``impl="torch"`` is a plain PyTorch implementation of the same math used as
 the numerics reference (and for CPU tests).
@@ -204,6 +210,38 @@ class LlamaBlock(nn.Module):
         g, u = F.linear(y, self.w13.weight).chunk(2, dim=-1)
         return h, F.linear(F.silu(g) * u, self.w2.weight)
 
+    def extend(self, h, delta, rope, cache, layer: int, T: int, n_new, hip: bool):
+        """``T`` new tokens per batch row (``h`` [B*T, dim], rows ordered
+        ``(batch, t)``) against the cache: the block with ``M = B*T``, the
+        live tokens' K/V appended at ``cache.lens + t`` and token ``t``
+        attending to ``cache.lens + t + 1`` keys (``n_new``: int32 [B], real
+        tokens per row)."""
+        from ..ops import llm
+
+        c = self.cfg
+        k, v = cache.k[layer], cache.v[layer]
+        if hip:
+            if delta is None:
+                y = llm.rmsnorm(h, self.attn_norm, c.norm_eps)
+            else:
+                h, y = llm.add_rmsnorm(h, delta, self.attn_norm, c.norm_eps)
+            qkv = _lin_rows(y, self.wqkv)
+            llm.rope_kv_extend(qkv, rope[0], rope[1], k, v, cache.lens, n_new, T, c.n_heads, c.n_kv_heads)
+            ctx = llm.attention_extend(qkv, k, v, cache.lens, n_new, T, c.n_heads, c.n_kv_heads,
+                                       impl="sdpa" if ATTN_IMPL == "sdpa" else None)
+            h, y = llm.add_rmsnorm(h, _lin_rows(ctx, self.wo), self.ffn_norm, c.norm_eps)
+            return h, _lin_rows(_lin_rows(y, self.w13, swiglu=True), self.w2)
+        if delta is not None:
+            h = h + delta
+        y = _rmsnorm_ref(h, self.attn_norm, c.norm_eps)
+        qkv = F.linear(y, self.wqkv.weight)
+        llm.rope_kv_extend(qkv, rope[0], rope[1], k, v, cache.lens, n_new, T, c.n_heads, c.n_kv_heads, impl="torch")
+        ctx = llm.attention_extend(qkv, k, v, cache.lens, n_new, T, c.n_heads, c.n_kv_heads, impl="torch")
+        h = h + F.linear(ctx, self.wo.weight)
+        y = _rmsnorm_ref(h, self.ffn_norm, c.norm_eps)
+        g, u = F.linear(y, self.w13.weight).chunk(2, dim=-1)
+        return h, F.linear(F.silu(g) * u, self.w2.weight)
+
 
 class KVCache:
     """The state of one generation: per layer the rotated keys and the values
@@ -247,6 +285,19 @@ def _lin_decode(x, w, swiglu: bool = False):
     from ..ops import gemm
 
     return gemm.linear_decode(x, w, swiglu)
+
+
+def _lin_rows(x, mod: nn.Linear, swiglu: bool = False):
+    """A linear layer of :meth:`LlamaBlock.extend` (``x [B*T, k_in]``), by row
+    count: up to the skinny kernel's 16 rows the decode step's call
+    (:func:`_lin_decode`), above it the training forward's (:func:`_lin` and
+    ``llm.swiglu``)."""
+    from ..ops import gemm, llm
+
+    if x.shape[0] <= gemm.SKINNY_MAX_ROWS:
+        return _lin_decode(x, mod.weight, swiglu)
+    y = _lin(x, mod)
+    return llm.swiglu(y) if swiglu else y
 
 
 def _plan(kind: str, x, mod: nn.Linear) -> str:
@@ -409,19 +460,92 @@ class Llama(nn.Module):
         return acc
 
     @torch.no_grad()
-    def prefill(self, tokens: torch.Tensor, lens: torch.Tensor | None, cache: KVCache):
+    def extend(self, tokens: torch.Tensor, cache: KVCache, n_new: torch.Tensor | None = None, logits: str = "all"):
+        """Feed ``T`` more tokens per row, ``tokens`` [B, T] right-padded, to a
+        cache that holds ``cache.lens`` tokens already (zero after
+        ``cache.reset()``): one pass over the weights for all of them, on the
+        kernels of ``csrc/kernels/attn_extend.hip``.  ``n_new`` (int32 [B] on
+        the device; None: T for every row) counts the real tokens of each
+        row.  Token ``t`` of row ``b`` is live iff ``t < n_new[b]`` and
+        ``cache.lens[b] + t < cache.max_len``; the live tokens are appended
+        and each attends to the history plus the chunk up to itself, then
+        ``cache.lens`` advances by the live count (a torch op on the device;
+        nothing here syncs with the host).  ``cache.step`` / ``cache.done``
+        are not touched.
+
+        Returns the logits ``[B, T, V]`` (rows of tokens that are not live
+        are meaningless), or with ``logits="last"`` ``[B, V]`` at each row's
+        last live token, the head GEMM then running on B rows only (a row
+        with no live token gets its row 0, which is meaningless).  Leaves
+        ``training``, every ``.grad`` and ``last_z_loss`` alone."""
+        if tokens.dim() != 2:
+            raise ValueError(f"extend: tokens must be [B, T], got {tuple(tokens.shape)}")
+        B, T = tokens.shape
+        if B != cache.batch or T < 1 or T > cache.max_len:
+            raise ValueError(f"extend: {B} x {T} tokens do not fit a {cache.batch} x {cache.max_len} cache")
+        if logits not in ("all", "last"):
+            raise ValueError(f"extend: logits must be all|last, got {logits!r}")
+        dev = tokens.device
+        if n_new is None:
+            n_new = torch.full((B,), T, device=dev, dtype=torch.int32)
+        elif n_new.dtype != torch.int32 or n_new.shape != (B,):
+            raise ValueError(f"extend: n_new must be int32 [{B}]")
+        hip = self.impl == "hip"
+        rope = self.rope(cache.max_len, dev)
+        h = self.tok_emb(tokens).reshape(B * T, self.cfg.dim)
+        delta = None
+        for i, blk in enumerate(self.layers):
+            h, delta = blk.extend(h, delta, rope, cache, i, T, n_new, hip)
+        if hip:
+            from ..ops import llm
+
+            y = llm.add_rmsnorm(h, delta, self.norm, self.cfg.norm_eps)[1]
+        else:
+            y = _rmsnorm_ref(h + delta, self.norm, self.cfg.norm_eps)
+        ar = torch.arange(T, device=dev)[None, :]
+        pos = cache.lens.long()[:, None] + ar
+        live = (ar < n_new[:, None]) & (pos >= 0) & (pos < cache.max_len)
+        if logits == "last":
+            last = (live * (ar + 1)).amax(1).sub(1).clamp_min(0)[:, None, None].expand(B, 1, self.cfg.dim)
+            z = self._head(y.view(B, T, self.cfg.dim).gather(1, last)[:, 0].contiguous(), decode=True)
+        else:
+            z = self._head(y, decode=B * T <= 16).view(B, T, -1)
+        cache.lens += live.sum(1).to(cache.lens.dtype)
+        return z
+
+    @torch.no_grad()
+    def prefill(self, tokens: torch.Tensor, lens: torch.Tensor | None, cache: KVCache, chunk: int | None = None):
         """Run the right-padded prompts ``tokens`` [B, P] through the training
         forward path, copy every layer's rotated K and its V into ``cache``
         and set ``cache.lens`` to ``lens`` (int32 [B] on the device; None: P
         for every row).  Returns the logits ``[B, V]`` at each row's last real
         position.  Causality keeps the padding out of every real position,
-        and what the padding leaves in the cache lies past ``lens``."""
+        and what the padding leaves in the cache lies past ``lens``.
+
+        ``chunk=c`` (chunked prefill) resets the cache and feeds the prompts
+        ``c`` positions at a time through :meth:`extend` instead: activations
+        of ``B*c`` rows at most, the package's own attention kernel for any
+        prompt length and for head_dim 64, nothing of the padding in the
+        cache.  Each row keeps the logits of the chunk that holds its last
+        real position (a device-side ``where``, no sync).  The rounding
+        differs from the unchunked path's."""
         B, P = tokens.shape
         c = self.cfg
         if B != cache.batch or P > cache.max_len:
             raise ValueError(f"prefill: {B} x {P} prompts do not fit a {cache.batch} x {cache.max_len} cache")
         if lens is None:
             lens = torch.full((B,), P, device=tokens.device, dtype=torch.int32)
+        if chunk is not None:
+            if int(chunk) != chunk or chunk < 1:
+                raise ValueError(f"prefill: chunk must be an integer >= 1 or None, got {chunk}")
+            chunk = int(chunk)
+            cache.reset()
+            out = None
+            for i in range(0, P, chunk):
+                n = (lens - i).clamp(0, min(chunk, P - i)).to(torch.int32)
+                z = self.extend(tokens[:, i:i + chunk], cache, n_new=n, logits="last")
+                out = z if out is None else torch.where((n > 0)[:, None], z, out)
+            return out
         kv = []
         y = self._final_hidden(tokens, kv=kv)
         H, Hkv = c.n_heads, c.n_kv_heads
@@ -460,7 +584,7 @@ class Llama(nn.Module):
     @torch.no_grad()
     def generate(self, prompts: torch.Tensor, prompt_lens=None, max_new_tokens: int = 16, temperature: float = 0.0,
                  top_k: int = 0, eos_id: int | None = None, seed: int = 0, graph: bool = False,
-                 return_logits: bool = False, cache: KVCache | None = None):
+                 return_logits: bool = False, cache: KVCache | None = None, prefill_chunk: int | None = None):
         """Generate ``max_new_tokens`` tokens after each prompt: ``[B,
         max_new_tokens]`` int64 on the device (with ``return_logits`` also the
         ``[B, max_new_tokens, V]`` logits each token was chosen from).
@@ -478,6 +602,8 @@ class Llama(nn.Module):
         host.  ``graph=True`` warms one step eagerly, restores the step state,
         captures decode_step + sample + advance once and replays it for every
         token after the first; it returns the tokens of ``graph=False``.
+        ``prefill_chunk`` is :meth:`prefill`'s ``chunk`` (None: the unchunked
+        path).
 
         Leaves ``training``, every ``.grad`` and ``last_z_loss`` alone.
         Raises ValueError when ``max(prompt_lens) + max_new_tokens`` exceeds
@@ -512,7 +638,7 @@ class Llama(nn.Module):
         opts = dict(u=u, temperature=temperature, top_k=top_k, cur=cur, out=out, step=cache.step, done=cache.done,
                     eos_id=eos_id, advance=True, impl=None if self.impl == "hip" else "torch")
 
-        logits = self.prefill(prompts, lens, cache)
+        logits = self.prefill(prompts, lens, cache, chunk=prefill_chunk)
         if kept is not None:
             kept[:, 0].copy_(logits)
         llm.sample(logits, **opts)  # the first token is not in the cache yet: lens stays

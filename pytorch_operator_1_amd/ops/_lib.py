@@ -31,7 +31,7 @@ HIPCC = os.environ.get("HIPCC", shutil.which("hipcc") or "/opt/rocm/bin/hipcc")
 HIP_SOURCES = ("kernels/mnist_kernels.hip", "kernels/common_kernels.hip", "kernels/optim_kernels.hip",
                "kernels/llm_kernels.hip", "kernels/attention.hip", "kernels/bn_kernels.hip", "kernels/conv3x3.hip",
                "kernels/conv3x3_wgrad.hip", "kernels/gemm_bf16.hip", "comm/xgmi_allreduce.hip", "kernels/decode.hip",
-               "kernels/gemm_skinny.hip")
+               "kernels/gemm_skinny.hip", "kernels/attn_extend.hip")
 
 _lock = threading.Lock()
 # launchers return an int hipError; these few return something else
@@ -199,6 +199,11 @@ _SIGS = {
     "pto_attn_decode_chunk": [_I, _I],
     "pto_attn_decode": [_P, _L, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _P],
     "pto_sample": [_P, _P, _P, _P, _I, _P, _P, _I, _I, _F, _I, _L, _I, _P, _P],
+    # multi-token extend on the KV cache: T-token append, MFMA attention (csrc/kernels/attn_extend.hip)
+    "pto_rope_kv_extend": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P],
+    "pto_attn_extend_supported": [_I, _I, _I],
+    "pto_attn_extend_chunk": [_I, _I],
+    "pto_attn_extend": [_P, _L, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _F, _P],
     # xGMI peer all-reduce (csrc/comm/xgmi_allreduce.hip)
     "pto_ar_ipc_handle_size": [],
     "pto_ar_flag_bytes": [_I],

@@ -13,7 +13,11 @@ entropy: plain NLL and top-1 / top-k counts summed on the device.
 The generation ops at the end of the file (``csrc/kernels/decode.hip``) --
 :func:`rope_kv_append`, :func:`attention_decode`, :func:`sample` -- are
 inference only and also run on CPU tensors and unsupported shapes, through
-torch implementations of the same rules.
+torch implementations of the same rules.  So do the multi-token ops after
+them (``csrc/kernels/attn_extend.hip``): :func:`rope_kv_extend` appends ``T``
+tokens per row and :func:`attention_extend` runs their ``T * H`` query rows
+against the cache on an MFMA kernel (chunked prefill, continuation on a
+filled cache, verification of a block of draft tokens).
 """
 from __future__ import annotations
 
@@ -703,3 +707,147 @@ def sample(logits, u=None, temperature: float = 0.0, top_k: int = 0, cur=None, o
         if lens is not None:
             lens += 1
     return cur
+
+
+# ---------------------------------------------------------------- multi-token extend on the KV cache
+# (csrc/kernels/attn_extend.hip): T new tokens per row against the cached
+# history -- chunked prefill, a follow-up turn on a cache that already holds
+# one, a block of draft tokens verified in one pass.  Token t of row b is live
+# iff ``0 <= t < n_new[b]`` and ``0 <= lens[b] + t < limit``; both vectors stay
+# on the device and no launch parameter depends on them.
+
+
+def _live(lens, n_new, T: int, limit: int):
+    """``(pos [B, T], live [B, T])`` from the device lengths."""
+    pos = lens.long()[:, None] + torch.arange(T, device=lens.device)[None, :]
+    return pos, (torch.arange(T, device=lens.device)[None, :] < n_new[:, None]) & (pos >= 0) & (pos < limit)
+
+
+def rope_kv_extend(qkv, cos, sin, k_cache, v_cache, lens, n_new, T: int, n_heads: int, n_kv_heads: int,
+                   impl: str | None = None):
+    """Append ``T`` new tokens per batch row to the KV cache.
+
+    ``qkv`` ``[B*T, (H + 2*Hkv)*D]`` is the fused QKV projection of the new
+    tokens, rows ordered ``(batch, t)``; ``lens`` (int32 ``[B]``, device) the
+    cache length BEFORE the append and ``n_new`` (int32 ``[B]``) the count of
+    real tokens of the right-padded chunk.  For every live token (``t <
+    n_new[b]`` and ``0 <= p = lens[b] + t < min(max_len, table length)``) the
+    ``H`` query heads are rotated in place at position ``p`` and the rotated K
+    head and the V head go to ``k_cache[b, :, p]`` / ``v_cache[b, :, p]``, with
+    :func:`rope_`'s arithmetic: bitwise the key prefill produces there.  A
+    token that is not live writes nothing and its row is left alone.  Returns
+    ``qkv``; ``lens`` is not advanced."""
+    B, Hkv, max_len, D = k_cache.shape
+    H, T = int(n_heads), int(T)
+    if Hkv != n_kv_heads or v_cache.shape != k_cache.shape:
+        raise ValueError("rope_kv_extend: caches must both be [B, Hkv, max_len, D]")
+    if T < 1 or T > max_len:
+        raise ValueError(f"rope_kv_extend: T must be in [1, max_len = {max_len}], got {T}")
+    if qkv.shape != (B * T, (H + 2 * Hkv) * D) or not qkv.is_contiguous():
+        raise ValueError(f"rope_kv_extend: qkv must be contiguous [B*T, (H + 2*Hkv)*D], got {tuple(qkv.shape)}")
+    if cos.shape != sin.shape or cos.shape[-1] != D // 2:
+        raise ValueError("rope_kv_extend: cos/sin must be [positions, D/2]")
+    _i32(lens, "rope_kv_extend: lens", B)
+    _i32(n_new, "rope_kv_extend: n_new", B)
+    if impl != "torch" and _hip_bf16(qkv, k_cache, v_cache) and D % 8 == 0 and k_cache.is_contiguous() \
+            and v_cache.is_contiguous():
+        cos, sin = cos.contiguous(), sin.contiguous()
+        if cos.dtype != torch.float32 or sin.dtype != torch.float32:
+            raise TypeError("rope_kv_extend: fp32 cos/sin tables required")
+        _lib.check(_lib.lib().pto_rope_kv_extend(qkv.data_ptr(), cos.data_ptr(), sin.data_ptr(), k_cache.data_ptr(),
+                                                 v_cache.data_ptr(), lens.data_ptr(), n_new.data_ptr(), B, T, H, Hkv,
+                                                 D, max_len, cos.shape[0], _lib.stream_ptr(qkv.device)),
+                   "rope_kv_extend")
+        return qkv
+    limit = min(max_len, cos.shape[0])
+    pos, live = _live(lens, n_new, T, limit)
+    pc = pos.clamp(0, limit - 1)
+    c = torch.cat([cos[pc], cos[pc]], -1)[:, :, None, :].float()  # [B, T, 1, D]
+    s = torch.cat([sin[pc], sin[pc]], -1)[:, :, None, :].float()
+    v4 = qkv.view(B, T, H + 2 * Hkv, D)
+    rot = v4[:, :, :H + Hkv].float()
+    rot = (rot * c + _rotate_half(rot) * s).to(qkv.dtype)
+    ok = live[:, :, None, None]
+    v4[:, :, :H] = torch.where(ok, rot[:, :, :H], v4[:, :, :H])
+    # (lens + t) mod max_len is p for a live token and a slot of its own for every other one (T <= max_len),
+    # which gets back what it held: one scatter without duplicate indices and without a host sync
+    idx = torch.remainder(pos, max_len)[:, None, :, None].expand(B, Hkv, T, D)
+    okc = live[:, None, :, None]
+    for cache, new in ((k_cache, rot[:, :, H:]), (v_cache, v4[:, :, H + Hkv:])):
+        cache.scatter_(2, idx, torch.where(okc, new.transpose(1, 2).to(cache.dtype), cache.gather(2, idx)))
+    return qkv
+
+
+def attention_extend_supported(H: int, Hkv: int, head_dim: int) -> bool:
+    """Shapes the MFMA extend kernel covers: head_dim 64 or 128 and a GQA
+    group ``H / Hkv`` of 1, 2, 4 or 8 (any ``T``)."""
+    return Hkv > 0 and H % Hkv == 0 and head_dim in (64, 128) and H // Hkv in (1, 2, 4, 8)
+
+
+def extend_row_tiles(T: int, H: int, Hkv: int) -> int:
+    """32-row query tiles per (batch row, KV head): ``ceil(T * G / 32)``."""
+    return -(-int(T) * (int(H) // int(Hkv)) // 32)
+
+
+def attention_extend(q, k_cache, v_cache, lens, n_new, T: int, n_heads: int, n_kv_heads: int,
+                     n_splits: int | None = None, impl: str | None = None):
+    """``T`` new query tokens per row against the cache: ``O [B*T, H*D]``.
+
+    Runs AFTER :func:`rope_kv_extend` with the same ``lens`` / ``n_new``, so it
+    reads only the caches ``[B, Hkv, max_len, D]``.  ``q`` holds the rotated
+    query heads of row ``b*T + t`` in its first ``H*D`` columns -- the fused
+    QKV rows ``[B*T, (H + 2*Hkv)*D]`` as they are, or ``[B*T, H*D]``.  Token
+    ``t`` of row ``b`` attends to the keys ``[0, lens[b] + t + 1)``; a token
+    that is not live (``t >= n_new[b]`` or ``lens[b] + t`` outside ``[0,
+    max_len)``) gives zeros, and nothing at or past ``lens[b] +`` (live
+    tokens) is used.  ``n_splits`` workgroups share one (32-row tile, KV
+    head)'s history, each taking :func:`decode_chunk` keys, and a second
+    launch folds their partial softmaxes in split order; the output bits
+    depend on ``(inputs, lens, n_new, T, max_len, n_splits)`` only.  The
+    default reuses :func:`decode_splits` with ``B * row_tiles`` in place of
+    ``B``; that choice is NOT measured (profiles/extend.md).
+    ``impl="sdpa"`` / ``"torch"``, CPU tensors and shapes outside
+    :func:`attention_extend_supported` use torch's SDPA with a mask built from
+    the device lengths."""
+    B, Hkv, max_len, D = k_cache.shape
+    H, T = int(n_heads), int(T)
+    if Hkv != n_kv_heads or v_cache.shape != k_cache.shape or H % Hkv:
+        raise ValueError("attention_extend: caches must both be [B, Hkv, max_len, D] with H % Hkv == 0")
+    if T < 1 or T > max_len:
+        raise ValueError(f"attention_extend: T must be in [1, max_len = {max_len}], got {T}")
+    if q.dim() != 2 or q.shape[0] != B * T or q.shape[1] < H * D or q.stride(1) != 1:
+        raise ValueError(f"attention_extend: q must be [B*T, >= H*D] with unit inner stride, got {tuple(q.shape)}")
+    _i32(lens, "attention_extend: lens", B)
+    _i32(n_new, "attention_extend: n_new", B)
+    if n_splits is not None and (int(n_splits) != n_splits or n_splits < 1):
+        raise ValueError(f"attention_extend: n_splits must be an integer >= 1, got {n_splits}")
+    if impl not in (None, "hip", "sdpa", "torch"):
+        raise ValueError(f"attention_extend: impl must be hip|sdpa|torch, got {impl!r}")
+    tiles = extend_row_tiles(T, H, Hkv)
+    if impl in (None, "hip") and _hip_bf16(q, k_cache, v_cache) and attention_extend_supported(H, Hkv, D) \
+            and k_cache.is_contiguous() and v_cache.is_contiguous() and B * tiles <= 65535:
+        if q.stride(0) % 8 or q.data_ptr() % 16:
+            q = q[:, :H * D].contiguous()
+        ns = decode_splits(B * tiles, Hkv, max_len) if n_splits is None else int(n_splits)
+        o = torch.empty(B * T, H * D, device=q.device, dtype=q.dtype)
+        ml = po = None
+        if ns > 1:
+            ml = torch.empty(B * T, H, ns, 2, device=q.device, dtype=torch.float32)
+            po = torch.empty(B * T, H, ns, D, device=q.device, dtype=torch.float32)
+        _lib.check(_lib.lib().pto_attn_extend(q.data_ptr(), q.stride(0), k_cache.data_ptr(), v_cache.data_ptr(),
+                                              lens.data_ptr(), n_new.data_ptr(), o.data_ptr(), _p(ml), _p(po), B, T, H,
+                                              Hkv, D, max_len, ns, D ** -0.5, _lib.stream_ptr(q.device)), "attn_extend")
+        return o
+    pos, live = _live(lens, n_new, T, max_len)
+    keys = torch.arange(max_len, device=q.device)[None, None, :]
+    mask = (live[:, :, None] & (keys <= pos[:, :, None]))[:, None]  # [B, 1, T, max_len]
+    valid = mask.any(2)[:, :, :, None]  # [B, 1, max_len, 1]: a key some live token sees
+    zero = torch.zeros((), device=q.device, dtype=k_cache.dtype)
+    k = torch.where(valid, k_cache, zero)  # whatever lies past the live tokens is discarded, never multiplied
+    v = torch.where(valid, v_cache, zero)
+    q4 = q[:, :H * D].reshape(B, T, H, D).transpose(1, 2)
+    q4 = torch.where(live[:, None, :, None], q4, torch.zeros((), device=q.device, dtype=q.dtype))
+    o = torch.nn.functional.scaled_dot_product_attention(q4, k.to(q.dtype), v.to(q.dtype), attn_mask=mask,
+                                                         enable_gqa=Hkv != H)
+    o = torch.where(live[:, None, :, None], o, torch.zeros((), device=q.device, dtype=o.dtype))
+    return o.transpose(1, 2).reshape(B * T, H * D)

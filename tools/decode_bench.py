@@ -28,9 +28,18 @@ the next of several weight copies (at least 768 MB in rotation); the two
 sides alternate round by round in one process; bytes/s counts the weight
 bytes once.  Then a sweep of ``n_splits`` for the ``wo`` / ``w2`` shapes.
 
+``--part extend`` (profiles/extend.md): ``ops.llm.attention_extend`` at the
+same head shape, T in {1, 4, 8, 16, 64} new tokens per row after a history of
+1024 / 8192 / 32768 keys, B in {1, 8}, with the same rotation of cache copies:
+the owned MFMA kernel with the default split count and over an ``n_splits``
+sweep, SDPA with an explicit mask on the same cache, and T successive
+``attention_decode`` calls (which share one cache copy).  Then
+``Llama.prefill`` of ``4 * --prompt`` tokens unchunked against ``chunk=128``
+and ``chunk=512``.
+
 One JSON line per row.
 
-    python tools/decode_bench.py [--part attn|generate|linear|all] [--rounds 15] [--reps 20]
+    python tools/decode_bench.py [--part attn|generate|linear|extend|all] [--rounds 15] [--reps 20]
                                  [--models llama3-1b] [--prompt 512] [--new 128] [--repeats 3]
 """
 from __future__ import annotations
@@ -270,9 +279,110 @@ def generate(args):
         torch.cuda.empty_cache()
 
 
+def extend(args):
+    """T new tokens per row against ``history`` cached keys (lens = history, every token live)."""
+    import torch
+    import torch.nn.functional as F
+
+    from pytorch_operator_1_amd.ops import llm
+
+    dev = torch.device("cuda")
+    for B in (1, 8):
+        for hist in (1024, 8192, 32768):
+            for T in (1, 4, 8, 16, 64):
+                max_len = hist + T
+                kv_bytes = 2 * B * HKV * max_len * D * 2
+                ncopy = max(2, -(-LLC_BYTES // kv_bytes))
+                g = torch.Generator(device=dev).manual_seed(0)
+                ks = [torch.randn(B, HKV, max_len, D, device=dev, dtype=torch.bfloat16, generator=g)
+                      for _ in range(ncopy)]
+                vs = [torch.randn(B, HKV, max_len, D, device=dev, dtype=torch.bfloat16, generator=g)
+                      for _ in range(ncopy)]
+                q = torch.randn(B * T, H * D, device=dev, dtype=torch.bfloat16, generator=g)
+                lens = torch.full((B,), hist, device=dev, dtype=torch.int32)
+                n_new = torch.full((B,), T, device=dev, dtype=torch.int32)
+                steps = [lens + t + 1 for t in range(T)]  # the lengths of T successive decode steps
+                qt = [q.view(B, T, H * D)[:, t].contiguous() for t in range(T)]
+                q4 = q.view(B, T, H, D).transpose(1, 2)
+                mask = (torch.arange(max_len, device=dev)[None, :] <= hist + torch.arange(T, device=dev)[:, None])
+                turn = [0]
+
+                def nxt():
+                    turn[0] = (turn[0] + 1) % ncopy
+                    return ks[turn[0]], vs[turn[0]]
+
+                def owned(ns=None):
+                    k, v = nxt()
+                    return llm.attention_extend(q, k, v, lens, n_new, T, H, HKV, n_splits=ns)
+
+                def sdpa_mask():
+                    k, v = nxt()
+                    return F.scaled_dot_product_attention(q4, k, v, attn_mask=mask, enable_gqa=True)
+
+                def decode_steps():
+                    k, v = nxt()  # one copy for the T steps: the later ones may find it in the cache
+                    return [llm.attention_decode(qt[t], k, v, steps[t], H, HKV) for t in range(T)]
+
+                turn[0] = 0
+                o = owned().float()
+                turn[0] = 0
+                ref = sdpa_mask().transpose(1, 2).reshape(B * T, H * D).float()  # the same cache copy
+                err = float((o - ref).norm() / ref.norm())
+                tiles = llm.extend_row_tiles(T, H, HKV)
+                default = llm.decode_splits(B * tiles, HKV, max_len)
+                base = {"B": B, "history": hist, "T": T, "kv_MB": round(kv_bytes / 2**20, 1), "cache_copies": ncopy,
+                        "rounds": args.rounds, "reps": args.reps}
+
+                def row(case, med, mn, **kw):
+                    print(json.dumps({**base, "case": case, **kw, "median_us": round(med, 2), "min_us": round(mn, 2),
+                                      "TBps_median": round(kv_bytes / med / 1e6, 3)}), flush=True)
+
+                row("extend (default splits)", *timed(owned, args.rounds, args.reps), n_splits=default,
+                    relerr_vs_sdpa=round(err, 5))
+                row("sdpa, explicit mask", *timed(sdpa_mask, args.rounds, args.reps))
+                row("T attention_decode calls", *timed(decode_steps, args.rounds, max(2, args.reps // 4)))
+                ns = 1
+                while ns <= min(256, max_len // 64):
+                    row("extend, n_splits sweep", *timed(lambda: owned(ns), args.rounds, args.reps), n_splits=ns)
+                    ns *= 4
+                del ks, vs
+                torch.cuda.empty_cache()
+    prefill(args)
+
+
+def prefill(args):
+    """``Llama.prefill`` of a ``--prompt * 4``-token prompt, unchunked against ``chunk=`` (host clock, synchronised)."""
+    import torch
+
+    from pytorch_operator_1_amd.models.llama import CONFIGS, KVCache, Llama
+
+    dev = torch.device("cuda")
+    for name in args.models.split(","):
+        torch.manual_seed(0)
+        model = Llama(CONFIGS[name], impl="hip", device=dev)
+        P = args.prompt * 4
+        for B in (1, 8):
+            tok = torch.randint(0, model.cfg.vocab_size, (B, P), device=dev)
+            cache = KVCache(model.cfg, B, P, dev)
+            for chunk in (None, 128, 512):
+                ts = []
+                for _ in range(args.repeats + 1):  # the first run warms up
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    model.prefill(tok, None, cache, chunk=chunk)
+                    torch.cuda.synchronize()
+                    ts.append((time.perf_counter() - t0) * 1e3)
+                ts = sorted(ts[1:])
+                print(json.dumps({"case": "prefill", "model": name, "B": B, "prompt": P, "chunk": chunk,
+                                  "median_ms": round(ts[len(ts) // 2], 2), "min_ms": round(ts[0], 2),
+                                  "repeats": args.repeats}), flush=True)
+        del model
+        torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--part", choices=["attn", "generate", "linear", "all"], default="all")
+    ap.add_argument("--part", choices=["attn", "generate", "linear", "extend", "all"], default="all")
     ap.add_argument("--rounds", type=int, default=15)
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--models", default="llama3-1b")
@@ -292,6 +402,8 @@ def main():
         linear(args)
     if args.part in ("generate", "all"):
         generate(args)
+    if args.part in ("extend", "all"):
+        extend(args)
 
 
 if __name__ == "__main__":

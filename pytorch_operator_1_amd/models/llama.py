@@ -192,13 +192,13 @@ class LlamaBlock(nn.Module):
                 y = llm.rmsnorm(h, self.attn_norm, c.norm_eps)
             else:
                 h, y = llm.add_rmsnorm(h, delta, self.attn_norm, c.norm_eps)
-            qkv = _lin_decode(y, self.wqkv.weight)
+            qkv = _lin_decode(y, self.wqkv)
             llm.rope_kv_append(qkv, rope[0], rope[1], k, v, cache.lens, c.n_heads, c.n_kv_heads)
             ctx = llm.attention_decode(qkv, k, v, cache.lens_incl, c.n_heads, c.n_kv_heads,
                                        impl="sdpa" if ATTN_IMPL == "sdpa" else None)
-            h, y = llm.add_rmsnorm(h, _lin_decode(ctx, self.wo.weight), self.ffn_norm, c.norm_eps)
+            h, y = llm.add_rmsnorm(h, _lin_decode(ctx, self.wo), self.ffn_norm, c.norm_eps)
             # on the skinny kernel the SwiGLU is w13's epilogue: no [B, 2F] round trip
-            return h, _lin_decode(_lin_decode(y, self.w13.weight, swiglu=True), self.w2.weight)
+            return h, _lin_decode(_lin_decode(y, self.w13, swiglu=True), self.w2)
         if delta is not None:
             h = h + delta
         y = _rmsnorm_ref(h, self.attn_norm, c.norm_eps)
@@ -278,13 +278,17 @@ def _lin(x, mod: nn.Linear, tstash=None):
     return gemm.linear(x, mod.weight, getattr(mod, "weight_t", None), getattr(mod, "dw_kcontig", False), tstash)
 
 
-def _lin_decode(x, w, swiglu: bool = False):
-    """A linear layer of the decode step (``x [B, k_in]``): the skinny GEMM
+def _lin_decode(x, mod, swiglu: bool = False):
+    """A linear layer of the decode step (``x [B, k_in]``; ``mod`` the module,
+    or a bare weight): the MX skinny GEMM on the module's quantised weight
+    where one is attached (:meth:`Llama.quantize_weights`), the skinny GEMM
     under ``PTO_SKINNY`` (:func:`..ops.gemm.skinny_plan`), else :func:`_lin`'s
     calls (and ``llm.swiglu``)."""
     from ..ops import gemm
 
-    return gemm.linear_decode(x, w, swiglu)
+    if isinstance(mod, torch.Tensor):
+        return gemm.linear_decode(x, mod, swiglu)
+    return gemm.linear_decode(x, mod.weight, swiglu, mx=getattr(mod, "weight_mx", None))
 
 
 def _lin_rows(x, mod: nn.Linear, swiglu: bool = False):
@@ -295,7 +299,7 @@ def _lin_rows(x, mod: nn.Linear, swiglu: bool = False):
     from ..ops import gemm, llm
 
     if x.shape[0] <= gemm.SKINNY_MAX_ROWS:
-        return _lin_decode(x, mod.weight, swiglu)
+        return _lin_decode(x, mod, swiglu)
     y = _lin(x, mod)
     return llm.swiglu(y) if swiglu else y
 
@@ -398,6 +402,39 @@ class Llama(nn.Module):
             if wt is not None:
                 llm.transpose_into(m.weight, wt)
 
+    @torch.no_grad()
+    def quantize_weights(self, fmt: str = "mxfp4", head: bool = True):
+        """Quantise every linear weight (:meth:`linear_modules`; the head only
+        with ``head`` and an untied embedding) to the MX format ``fmt``
+        (``"mxfp4"`` | ``"mxfp8"``, :func:`..ops.gemm.quantize_mx`): the
+        weight is overwritten in place with its dequantised values, which are
+        exact in bf16, and the packed form is attached as ``mod.weight_mx`` --
+        a plain attribute, so ``state_dict`` is unchanged.  Every path then
+        computes the same quantised model (training forward, prefill,
+        ``impl="torch"``, a model loaded from the state dict); the decode-time
+        linears (up to 16 rows) read the packed form through
+        :func:`..ops.gemm.skinny_mx_nt`.
+
+        The bf16 copies stay resident: this buys decode bandwidth, not
+        memory.  Any weight update (an optimizer step, ``load_state_dict``)
+        makes the attachments stale: call this again, or
+        :meth:`drop_quantized`."""
+        from ..ops import gemm
+
+        for m in self.linear_modules():
+            if m is self.lm_head and not head:
+                continue
+            q = gemm.quantize_mx(m.weight, fmt)
+            m.weight.copy_(gemm.dequantize_mx(q, m.weight.dtype))
+            m.weight_mx = q
+
+    def drop_quantized(self):
+        """Remove the attachments of :meth:`quantize_weights` (the weights
+        keep their dequantised values)."""
+        for m in self.linear_modules():
+            if hasattr(m, "weight_mx"):
+                del m.weight_mx
+
     def _head_weight(self):
         return self.tok_emb.weight if self.lm_head is None else self.lm_head.weight
 
@@ -435,7 +472,7 @@ class Llama(nn.Module):
             # the tied embedding leaves F.linear only for the skinny kernel
             if self.lm_head is not None or (y.dtype == w.dtype == torch.bfloat16 and
                                             gemm.skinny_plan(y.shape[0], w.shape[0], w.shape[1]) == "hip"):
-                return _lin_decode(y, w)
+                return _lin_decode(y, w if self.lm_head is None else self.lm_head)
         if self.impl == "hip" and self.lm_head is not None:
             return _lin(y, self.lm_head)
         return F.linear(y, self._head_weight())

@@ -341,13 +341,189 @@ def skinny_nt(x, w, out=None, out_dtype=None, swiglu: bool = False, n_splits: in
     return out
 
 
-def linear_decode(x, w, swiglu: bool = False):
+# ---------------------------------------------------------------- MX weight-only skinny GEMM (decode)
+# csrc/kernels/gemm_skinny_mx.hip: the skinny product against a weight held in
+# an OCP microscaling format -- blocks of 32 consecutive K elements of a row
+# share one E8M0 scale byte e (2^(e-127)); elements are e2m1 ("mxfp4", two per
+# byte, element 2i in the low nibble of byte i) or e4m3fn ("mxfp8").
+
+MX_FORMATS = {"mxfp4": 0, "mxfp8": 1}
+MX_BLOCK = 32
+_MX_EMAX = {"mxfp4": 2, "mxfp8": 8}  # exponent of the largest element: 6 = 1.5 * 2^2, 448 = 1.75 * 2^8
+_FP4_VALUES = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)
+# midpoints between neighbouring e2m1 magnitudes and whether a tie goes up (to the even code)
+_FP4_MIDPOINTS = ((0.25, False), (0.75, True), (1.25, False), (1.75, True), (2.5, False), (3.5, True), (5.0, False))
+
+
+class MXWeight:
+    """A weight ``[N, K]`` in an MX format: ``data`` uint8 ``[N, K/2]``
+    (``"mxfp4"``) or ``[N, K]`` (``"mxfp8"``), ``scales`` uint8 ``[N, K/32]``,
+    both contiguous."""
+
+    def __init__(self, data: torch.Tensor, scales: torch.Tensor, fmt: str, shape):
+        if fmt not in MX_FORMATS:
+            raise ValueError(f"fmt must be one of {tuple(MX_FORMATS)}, not {fmt!r}")
+        N, K = (int(s) for s in shape)
+        want = (N, K // 2 if fmt == "mxfp4" else K)
+        if K % MX_BLOCK or tuple(data.shape) != want or tuple(scales.shape) != (N, K // MX_BLOCK):
+            raise ValueError(f"MXWeight: data {tuple(data.shape)} / scales {tuple(scales.shape)} do not hold a {fmt} "
+                             f"weight of shape {(N, K)}")
+        if data.dtype != torch.uint8 or scales.dtype != torch.uint8 or data.device != scales.device:
+            raise TypeError("MXWeight: data and scales must be uint8 tensors on one device")
+        self.data, self.scales, self.fmt, self.shape = data.contiguous(), scales.contiguous(), fmt, (N, K)
+
+    @property
+    def device(self):
+        return self.data.device
+
+    def to(self, device):
+        return MXWeight(self.data.to(device), self.scales.to(device), self.fmt, self.shape)
+
+
+def _quantize_mx_torch(w: torch.Tensor, fmt: str):
+    N, K = w.shape
+    v = w.detach().float().reshape(N, K // MX_BLOCK, MX_BLOCK)
+    amax = v.abs().amax(-1)
+    # floor(log2(amax)) + 127 is the exponent field of amax (a subnormal clamps to e = 1 either way)
+    e = (((amax.view(torch.int32) >> 23) & 0xff) - _MX_EMAX[fmt]).clamp(1, 254)
+    e = torch.where(amax == 0, torch.full_like(e, 127), e)
+    v = v * ((254 - e) << 23).view(torch.float32)[..., None]  # times 2^(127 - e), exact
+    sign = torch.signbit(v)
+    if fmt == "mxfp4":
+        a = v.abs()
+        code = torch.zeros_like(a, dtype=torch.uint8)
+        for mid, tie_up in _FP4_MIDPOINTS:
+            code += (a >= mid) if tie_up else (a > mid)
+        nib = (code | (sign.to(torch.uint8) << 3)).reshape(N, K // 2, 2)
+        data = nib[..., 0] | (nib[..., 1] << 4)
+    else:
+        q = v.clamp(-448.0, 448.0).to(torch.float8_e4m3fn).view(torch.uint8)
+        data = ((q & 0x7f) | (sign.to(torch.uint8) << 7)).reshape(N, K)
+    return data.contiguous(), e.to(torch.uint8).contiguous()
+
+
+def quantize_mx(w: torch.Tensor, fmt: str = "mxfp4") -> MXWeight:
+    """Quantise a weight ``[N, K]`` (``K % 32 == 0``, finite values) by the
+    OCP MX v1.0 rule: per block of 32 along K, ``e = clamp(floor(log2(amax)) -
+    emax + 127, 1, 254)`` (127 for an all-zero block), each element ``w /
+    2^(e-127)`` rounded to nearest, ties to even on the element grid,
+    saturating at the largest element.  bf16 HIP tensors run the kernel
+    (``k_quant_mx``); everything else the same rule in torch."""
+    if fmt not in MX_FORMATS:
+        raise ValueError(f"fmt must be one of {tuple(MX_FORMATS)}, not {fmt!r}")
+    if w.dim() != 2 or w.shape[1] % MX_BLOCK or not w.is_floating_point():
+        raise ValueError(f"quantize_mx: a floating-point [N, K] weight with K % {MX_BLOCK} == 0 required, got "
+                         f"{w.dtype} {tuple(w.shape)}")
+    N, K = w.shape
+    if not (w.is_cuda and w.dtype == torch.bfloat16):
+        return MXWeight(*_quantize_mx_torch(w, fmt), fmt, (N, K))
+    w = _rows(w.detach())
+    data = torch.empty(N, K // 2 if fmt == "mxfp4" else K, device=w.device, dtype=torch.uint8)
+    scales = torch.empty(N, K // MX_BLOCK, device=w.device, dtype=torch.uint8)
+    rc = _lib.lib().pto_quant_mx(w.data_ptr(), w.stride(0) if N > 1 else K, data.data_ptr(), scales.data_ptr(),
+                                 MX_FORMATS[fmt], N, K, _lib.stream_ptr(w.device))
+    if rc == -1:
+        raise RuntimeError(f"quantize_mx: unsupported shape or layout: w {tuple(w.shape)} strides {w.stride()} "
+                           "(row stride a multiple of 8, 16-byte aligned pointer)")
+    _lib.check(rc, "quantize_mx")
+    return MXWeight(data, scales, fmt, (N, K))
+
+
+def dequantize_mx(q: MXWeight, dtype=torch.bfloat16) -> torch.Tensor:
+    """The ``[N, K]`` weight ``q`` stands for; exact in bf16 and wider."""
+    N, K = q.shape
+    scale = (q.scales.to(torch.int32) << 23).view(torch.float32)  # 2^(e - 127)
+    if q.fmt == "mxfp4":
+        nib = torch.stack((q.data & 0xf, q.data >> 4), dim=-1).reshape(N, K).long()
+        lut = torch.tensor(_FP4_VALUES + tuple(-v for v in _FP4_VALUES), device=q.device)
+        v = lut[nib]
+    else:
+        v = q.data.view(torch.float8_e4m3fn).float()
+    return (v.reshape(N, K // MX_BLOCK, MX_BLOCK) * scale[..., None]).reshape(N, K).to(dtype)
+
+
+def skinny_mx_takes(rows: int, n_out: int, k_in: int, swiglu: bool = False) -> bool:
+    """The MX skinny kernel's shape rules: 1..16 rows, weight rows a multiple
+    of 16 (of 32 with ``swiglu``), contraction a multiple of 128."""
+    if not 1 <= rows <= SKINNY_MAX_ROWS or n_out < 1 or k_in < 1:
+        return False
+    return n_out % (32 if swiglu else 16) == 0 and k_in % 128 == 0
+
+
+def skinny_mx_splits(n_out: int, k_in: int, fmt: str = "mxfp4") -> int:
+    """The MX kernel's default K split across workgroups: a function of the
+    layer shape and the format, never of the row count."""
+    return int(_lib.lib().pto_gemm_skinny_mx_splits(n_out, k_in, MX_FORMATS[fmt]))
+
+
+def skinny_mx_nt(x, q: MXWeight, out=None, out_dtype=None, swiglu: bool = False, n_splits: int | None = None):
+    """:func:`skinny_nt` against a quantised weight: ``x[M,K] @
+    dequantize_mx(q).T`` for ``1 <= M <= 16`` (bf16 ``x``, fp32 sums, bf16 or
+    fp32 out), the weight read in its packed form.  ``swiglu`` as in
+    :func:`skinny_nt`, bitwise :func:`..ops.llm.swiglu` of the plain bf16
+    result with the same ``n_splits`` (default :func:`skinny_mx_splits`).  Row
+    ``m`` of the result depends on ``x[m]``, ``q`` and ``n_splits`` only.  HIP
+    tensors launch the kernel and raise on a refused shape; CPU tensors
+    compute ``skinny_nt(x, dequantize_mx(q))``."""
+    if not isinstance(q, MXWeight):
+        raise TypeError(f"skinny_mx_nt: q must be an MXWeight, not {type(q).__name__}")
+    if x.dim() != 2 or x.shape[1] != q.shape[1]:
+        raise ValueError(f"skinny_mx_nt: operand shapes {tuple(x.shape)} and {q.shape} do not match")
+    (M, K), N = x.shape, q.shape[0]
+    if swiglu and N % 2:
+        raise ValueError(f"skinny_mx_nt: swiglu needs an even number of weight rows, got {N}")
+    oshape = (M, N // 2) if swiglu else (M, N)
+    if out is not None:
+        if tuple(out.shape) != oshape or out.device != x.device:
+            raise ValueError(f"skinny_mx_nt: out must be {oshape} on {x.device}")
+        if out_dtype is not None and out_dtype != out.dtype:
+            raise ValueError(f"skinny_mx_nt: out_dtype {out_dtype} != out.dtype {out.dtype}")
+        out_dtype = out.dtype
+    if not x.is_cuda:
+        return skinny_nt(x, dequantize_mx(q, x.dtype), out=out, out_dtype=out_dtype, swiglu=swiglu)
+    if x.dtype != torch.bfloat16 or q.device != x.device:
+        raise TypeError(f"skinny_mx_nt: bf16 x and the weight on one HIP device required (got {x.dtype} on "
+                        f"{x.device}, weight on {q.device})")
+    out_dtype = out_dtype or torch.bfloat16
+    if out_dtype not in (torch.bfloat16, torch.float32) or (swiglu and out_dtype != torch.bfloat16):
+        raise TypeError(f"skinny_mx_nt: output must be bf16{'' if swiglu else ' or fp32'}, not {out_dtype}")
+    if out is None:
+        out = torch.empty(oshape, device=x.device, dtype=out_dtype)
+    for t, what in ((x, "x"), (out, "out")):
+        if t.stride(1) != 1:
+            raise RuntimeError(f"skinny_mx_nt: {what} must have unit inner stride (strides {t.stride()})")
+    lda, ldc = (t.stride(0) if t.shape[0] > 1 else t.shape[1] for t in (x, out))
+    L = _lib.lib()
+    fmt = MX_FORMATS[q.fmt]
+    ns = int(L.pto_gemm_skinny_mx_splits(N, K, fmt)) if n_splits is None else int(n_splits)
+    nbytes = L.pto_gemm_skinny_mx_workspace(M, N, ns) if ns > 1 else 0
+    ws = _skinny_workspace(x.device, nbytes) if nbytes > 0 else None
+    rc = L.pto_gemm_skinny_mx(x.data_ptr(), lda, q.data.data_ptr(), q.scales.data_ptr(), out.data_ptr(), ldc,
+                              int(out_dtype == torch.float32), int(bool(swiglu)), fmt, M, N, K, ns, _lib.ptr(ws),
+                              nbytes if ws is not None else 0, _lib.stream_ptr(x.device))
+    if rc == -1:
+        raise RuntimeError(f"skinny_mx_nt: unsupported shape or layout: x {tuple(x.shape)} strides {x.stride()}, "
+                           f"{q.fmt} weight {q.shape}, out strides {out.stride()}, n_splits {ns} (1..16 rows, weight "
+                           "rows a multiple of 16 (32 with swiglu), contraction a multiple of 128, row strides "
+                           "multiples of 8, 16-byte aligned pointers, 1..64 splits)")
+    _lib.check(rc, "skinny_mx_nt")
+    return out
+
+
+def linear_decode(x, w, swiglu: bool = False, mx: MXWeight | None = None):
     """The bias-free linear layer of a decode step, ``x [B, k_in]`` against
     ``w [n_out, k_in]``, with ``swiglu`` the SwiGLU of a fused gate|up weight
-    applied to it.  bf16 HIP tensors under a ``"hip"`` :func:`skinny_plan`
-    take :func:`skinny_nt` (one launch, no ``[B, 2F]`` intermediate);
-    everything else makes the calls of :func:`linear` and
+    applied to it.  ``mx``: the quantised form of ``w``
+    (:func:`quantize_mx`; ``w`` holds its dequantised values); bf16 HIP
+    tensors of a shape :func:`skinny_mx_takes` then read it through
+    :func:`skinny_mx_nt` whatever ``PTO_SKINNY`` says -- attaching a quantised
+    weight is the opt-in.  Otherwise bf16 HIP tensors under a ``"hip"``
+    :func:`skinny_plan` take :func:`skinny_nt` (one launch, no ``[B, 2F]``
+    intermediate); everything else makes the calls of :func:`linear` and
     :func:`..ops.llm.swiglu`."""
+    if mx is not None and x.is_cuda and x.dim() == 2 and x.dtype == torch.bfloat16 \
+            and skinny_mx_takes(x.shape[0], mx.shape[0], mx.shape[1], swiglu):
+        return skinny_mx_nt(_rows(x), mx, swiglu=swiglu)
     if x.is_cuda and x.dim() == 2 and x.dtype == torch.bfloat16 and w.dtype == torch.bfloat16 \
             and skinny_takes(x.shape[0], w.shape[0], w.shape[1], swiglu) \
             and skinny_plan(x.shape[0], w.shape[0], w.shape[1]) == "hip":

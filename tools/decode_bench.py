@@ -37,9 +37,19 @@ sweep, SDPA with an explicit mask on the same cache, and T successive
 ``Llama.prefill`` of ``4 * --prompt`` tokens unchunked against ``chunk=128``
 and ``chunk=512``.
 
+``--part mx`` (profiles/decode_mx.md): the weight-only MXFP4 / MXFP8 skinny
+GEMM (``ops.gemm.skinny_mx_nt``) on the same layer shapes and row counts
+against ``skinny_nt`` and ``F.linear`` on the bf16 weight, all sides
+alternating round by round in one process, every side rotating over at least
+768 MB of ITS OWN weight bytes (bytes/s counts those once); a sweep of
+``n_splits`` at M = 1 for every shape and format; the graph-replayed decode
+step of ``Llama.generate`` at B in {1, 8} on bf16 weights (``PTO_SKINNY`` 0
+and 1) and after ``quantize_weights`` of each format; and, for information,
+the logits of the quantised llama3-mini against its unquantised self.
+
 One JSON line per row.
 
-    python tools/decode_bench.py [--part attn|generate|linear|extend|all] [--rounds 15] [--reps 20]
+    python tools/decode_bench.py [--part attn|generate|linear|extend|mx|all] [--rounds 15] [--reps 20]
                                  [--models llama3-1b] [--prompt 512] [--new 128] [--repeats 3]
 """
 from __future__ import annotations
@@ -380,9 +390,126 @@ def prefill(args):
         torch.cuda.empty_cache()
 
 
+def mx(args):
+    """Weight-only MXFP4 / MXFP8 decode linears against the bf16 paths."""
+    import torch
+    import torch.nn.functional as F
+
+    from pytorch_operator_1_amd.models.llama import CONFIGS, Llama
+    from pytorch_operator_1_amd.ops import gemm, llm
+
+    dev = torch.device("cuda")
+    fmts = ("mxfp4", "mxfp8")
+    bits = {"mxfp4": 4.25, "mxfp8": 8.25}
+    for name in args.models.split(","):
+        for layer, n_out, k_in in linear_shapes(CONFIGS[name]):
+            w_bytes = n_out * k_in * 2
+            ncopy = max(2, -(-LLC_BYTES // w_bytes))
+            g = torch.Generator(device=dev).manual_seed(0)
+            ws = [torch.randn(n_out, k_in, device=dev, dtype=torch.bfloat16, generator=g) * k_in ** -0.5
+                  for _ in range(ncopy)]
+            # each format rotates over at least LLC_BYTES of its own (smaller) bytes
+            qbytes = {f: int(n_out * k_in * bits[f] / 8) for f in fmts}
+            qs = {f: [gemm.quantize_mx(ws[i % ncopy], f) for i in range(max(2, -(-LLC_BYTES // qbytes[f])))]
+                  for f in fmts}
+            turn = {"bf16": 0, **{f: 0 for f in fmts}}
+
+            def nxt(kind):
+                pool = ws if kind == "bf16" else qs[kind]
+                turn[kind] = (turn[kind] + 1) % len(pool)
+                return pool[turn[kind]]
+
+            def row(case, med, mn, nbytes, **kw):
+                print(json.dumps({"part": "mx", "model": name, "layer": layer, "n_out": n_out, "k_in": k_in, **kw,
+                                  "case": case, "weight_MB": round(nbytes / 2**20, 1), "rounds": args.rounds,
+                                  "reps": args.reps, "median_us": round(med, 2), "min_us": round(mn, 2),
+                                  "TBps_median": round(nbytes / med / 1e6, 3),
+                                  "fraction_of_ceiling": round(nbytes / (med * 1e-6) / CEILING, 3)}), flush=True)
+
+            for M in (1, 8, 16):
+                x = torch.randn(M, k_in, device=dev, dtype=torch.bfloat16, generator=g)
+                sides = [(f"skinny_mx_nt {f}", (lambda f=f: gemm.skinny_mx_nt(x, nxt(f))), qbytes[f],
+                          gemm.skinny_mx_splits(n_out, k_in, f)) for f in fmts]
+                sides += [("skinny_nt", lambda: gemm.skinny_nt(x, nxt("bf16")), w_bytes,
+                           gemm.skinny_splits(n_out, k_in)),
+                          ("F.linear", lambda: F.linear(x, nxt("bf16")), w_bytes, None)]
+                if layer == "w13":
+                    sides += [(f"skinny_mx_nt {f} swiglu", (lambda f=f: gemm.skinny_mx_nt(x, nxt(f), swiglu=True)),
+                               qbytes[f], gemm.skinny_mx_splits(n_out, k_in, f)) for f in fmts]
+                    sides += [("skinny_nt swiglu", lambda: gemm.skinny_nt(x, nxt("bf16"), swiglu=True), w_bytes,
+                               gemm.skinny_splits(n_out, k_in)),
+                              ("F.linear + llm.swiglu", lambda: llm.swiglu(F.linear(x, nxt("bf16"))), w_bytes, None)]
+                res = timed_pair([s[1] for s in sides], args.rounds, args.reps)
+                for (case, _, nbytes, ns), (med, mn) in zip(sides, res):
+                    row(case, med, mn, nbytes, M=M, n_splits=ns)
+            x = torch.randn(1, k_in, device=dev, dtype=torch.bfloat16, generator=g)
+            sweep = [1, 2, 4, 8, 16, 32]
+            for f in fmts:
+                res = timed_pair([lambda n=n: gemm.skinny_mx_nt(x, nxt(f), n_splits=n) for n in sweep], args.rounds,
+                                 args.reps)
+                for n, (med, mn) in zip(sweep, res):
+                    row(f"skinny_mx_nt {f}, n_splits sweep", med, mn, qbytes[f], M=1, n_splits=n,
+                        default=gemm.skinny_mx_splits(n_out, k_in, f))
+            del ws, qs
+            torch.cuda.empty_cache()
+
+    # the graph-replayed decode step: bf16 weights on the library / on the skinny kernel, then quantised
+    for name in args.models.split(","):
+        torch.manual_seed(0)
+        model = Llama(CONFIGS[name], impl="hip", device=dev)
+        for B in (1, 8):
+            prompts = torch.randint(0, model.cfg.vocab_size, (B, args.prompt), device=dev,
+                                    generator=torch.Generator(device=dev).manual_seed(1))
+
+            def run(n_new, skinny):
+                os.environ["PTO_SKINNY"] = skinny
+                try:
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    model.generate(prompts, max_new_tokens=n_new, graph=n_new > 1)
+                    torch.cuda.synchronize()
+                    return time.perf_counter() - t0
+                finally:
+                    os.environ.pop("PTO_SKINNY", None)
+
+            def step_ms(skinny):
+                run(args.new, skinny)  # warm: code objects, the library's picks, the capture path
+                run(1, skinny)
+                pre = sorted(run(1, skinny) for _ in range(args.repeats))[args.repeats // 2]
+                tot = sorted(run(args.new, skinny) for _ in range(args.repeats))
+                return (tot[len(tot) // 2] - pre) / (args.new - 1) * 1e3, (tot[0] - pre) / (args.new - 1) * 1e3
+
+            cases = [("bf16, PTO_SKINNY=0", "0", None), ("bf16, PTO_SKINNY=1", "1", None),
+                     ("quantize_weights(mxfp4)", "0", "mxfp4"), ("quantize_weights(mxfp8)", "0", "mxfp8")]
+            for case, skinny, fmt in cases:
+                model.drop_quantized()
+                if fmt is not None:
+                    model.quantize_weights(fmt)
+                med, mn = step_ms(skinny)
+                print(json.dumps({"part": "mx", "case": "graph-replayed decode step", "weights": case, "model": name,
+                                  "B": B, "prompt": args.prompt, "new_tokens": args.new, "repeats": args.repeats,
+                                  "decode_ms_per_step": round(med, 4), "decode_ms_per_step_min": round(mn, 4)}),
+                      flush=True)
+            model.drop_quantized()
+        del model
+        torch.cuda.empty_cache()
+
+    # for information: logits of the quantised llama3-mini against its unquantised self
+    tok = torch.randint(0, 1024, (4, 128), device=dev, generator=torch.Generator(device=dev).manual_seed(2))
+    for f in fmts:
+        torch.manual_seed(0)
+        model = Llama(CONFIGS["llama3-mini"], impl="hip", device=dev)
+        with torch.no_grad():
+            ref = model(tok).double()
+            model.quantize_weights(f)
+            got = model(tok).double()
+        print(json.dumps({"part": "mx", "case": "llama3-mini logits, quantised vs unquantised", "fmt": f,
+                          "relerr": round(float((got - ref).norm() / ref.norm()), 5)}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--part", choices=["attn", "generate", "linear", "extend", "all"], default="all")
+    ap.add_argument("--part", choices=["attn", "generate", "linear", "extend", "mx", "all"], default="all")
     ap.add_argument("--rounds", type=int, default=15)
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--models", default="llama3-1b")
@@ -404,6 +531,8 @@ def main():
         generate(args)
     if args.part in ("extend", "all"):
         extend(args)
+    if args.part in ("mx", "all"):
+        mx(args)
 
 
 if __name__ == "__main__":

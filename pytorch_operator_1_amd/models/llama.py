@@ -288,6 +288,8 @@ def _lin_decode(x, mod, swiglu: bool = False):
 
     if isinstance(mod, torch.Tensor):
         return gemm.linear_decode(x, mod, swiglu)
+    if getattr(mod, "weight_packed", False):  # only the packed form exists
+        return gemm.linear_mx(x, mod.weight_mx, swiglu)
     return gemm.linear_decode(x, mod.weight, swiglu, mx=getattr(mod, "weight_mx", None))
 
 
@@ -295,10 +297,12 @@ def _lin_rows(x, mod: nn.Linear, swiglu: bool = False):
     """A linear layer of :meth:`LlamaBlock.extend` (``x [B*T, k_in]``), by row
     count: up to the skinny kernel's 16 rows the decode step's call
     (:func:`_lin_decode`), above it the training forward's (:func:`_lin` and
-    ``llm.swiglu``)."""
+    ``llm.swiglu``).  A module whose bf16 weight was released
+    (``quantize_weights(keep_bf16=False)``) reads its packed weight at any row
+    count (:func:`..ops.gemm.linear_mx`)."""
     from ..ops import gemm, llm
 
-    if x.shape[0] <= gemm.SKINNY_MAX_ROWS:
+    if x.shape[0] <= gemm.SKINNY_MAX_ROWS or getattr(mod, "weight_packed", False):
         return _lin_decode(x, mod, swiglu)
     y = _lin(x, mod)
     return llm.swiglu(y) if swiglu else y
@@ -348,6 +352,8 @@ class Llama(nn.Module):
         self.norm = nn.Parameter(torch.ones(cfg.dim, **kw))
         self.lm_head = None if cfg.tie_embeddings else nn.Linear(cfg.dim, cfg.vocab_size, bias=False, **kw)
         self._rope = {}
+        self._packed = False  # quantize_weights(keep_bf16=False): the bf16 linear weights are released
+        self.register_state_dict_pre_hook(lambda mod, prefix, keep_vars: mod._need_bf16("state_dict"))
         self.reset_parameters(init_std)
 
     @torch.no_grad()
@@ -386,6 +392,7 @@ class Llama(nn.Module):
         16 GB for Llama-3-8B) so each dgrad GEMM reads K-contiguous operands.
         The copies must be refreshed after every weight update
         (:meth:`refresh_transposed`)."""
+        self._need_bf16("enable_transposed_dgrad")
         for m in self.linear_modules():
             if getattr(m, "weight_t", None) is None:
                 w = m.weight
@@ -397,13 +404,14 @@ class Llama(nn.Module):
     def refresh_transposed(self):
         from ..ops import llm
 
+        self._need_bf16("refresh_transposed")
         for m in self.linear_modules():
             wt = getattr(m, "weight_t", None)
             if wt is not None:
                 llm.transpose_into(m.weight, wt)
 
     @torch.no_grad()
-    def quantize_weights(self, fmt: str = "mxfp4", head: bool = True):
+    def quantize_weights(self, fmt: str = "mxfp4", head: bool = True, keep_bf16: bool = True):
         """Quantise every linear weight (:meth:`linear_modules`; the head only
         with ``head`` and an untied embedding) to the MX format ``fmt``
         (``"mxfp4"`` | ``"mxfp8"``, :func:`..ops.gemm.quantize_mx`): the
@@ -418,19 +426,58 @@ class Llama(nn.Module):
         The bf16 copies stay resident: this buys decode bandwidth, not
         memory.  Any weight update (an optimizer step, ``load_state_dict``)
         makes the attachments stale: call this again, or
-        :meth:`drop_quantized`."""
+        :meth:`drop_quantized`.
+
+        ``keep_bf16=False`` (``impl="hip"`` with the weights on a HIP device,
+        else ValueError) releases them instead: each quantised module's
+        ``weight`` becomes an empty ``[0, k_in]`` tensor and the model runs
+        from the packed weights alone -- ``extend``, ``prefill`` (through
+        ``extend``; without ``chunk`` as one chunk), ``decode_step`` and
+        ``generate`` send every quantised linear through
+        :func:`..ops.gemm.linear_mx` at any row count, with the values the
+        default leaves in the bf16 weights.  The tied embedding is never
+        released.  What needs bf16 weights (``forward``, ``evaluate``, the
+        transposed copies, ``state_dict``) raises RuntimeError until
+        :meth:`restore_bf16_weights`."""
         from ..ops import gemm
 
+        if not keep_bf16 and (self.impl != "hip" or not all(m.weight.is_cuda for m in self.linear_modules())):
+            raise ValueError("quantize_weights: keep_bf16=False needs impl='hip' and the weights on a HIP device")
+        self._need_bf16("quantize_weights")
         for m in self.linear_modules():
             if m is self.lm_head and not head:
                 continue
             q = gemm.quantize_mx(m.weight, fmt)
-            m.weight.copy_(gemm.dequantize_mx(q, m.weight.dtype))
             m.weight_mx = q
+            if keep_bf16:
+                m.weight.copy_(gemm.dequantize_mx(q, m.weight.dtype))
+            else:
+                m.weight.data = torch.empty(0, m.weight.shape[1], device=m.weight.device, dtype=m.weight.dtype)
+                m.weight_packed = True
+        self._packed = not keep_bf16
+
+    def _need_bf16(self, what: str):
+        if self._packed:
+            raise RuntimeError(f"{what}: the bf16 linear weights were released by quantize_weights(keep_bf16=False); "
+                               "call restore_bf16_weights() first")
+
+    @torch.no_grad()
+    def restore_bf16_weights(self):
+        """Undo the release of ``quantize_weights(keep_bf16=False)``: every
+        released weight gets its dequantised values back -- the ones the
+        default ``keep_bf16=True`` leaves there -- and the attachments stay."""
+        from ..ops import gemm
+
+        for m in self.linear_modules():
+            if getattr(m, "weight_packed", False):
+                m.weight.data = gemm.dequantize_mx(m.weight_mx, m.weight.dtype)
+                del m.weight_packed
+        self._packed = False
 
     def drop_quantized(self):
         """Remove the attachments of :meth:`quantize_weights` (the weights
         keep their dequantised values)."""
+        self._need_bf16("drop_quantized")
         for m in self.linear_modules():
             if hasattr(m, "weight_mx"):
                 del m.weight_mx
@@ -464,7 +511,10 @@ class Llama(nn.Module):
     def _head(self, y, decode: bool = False):
         """The head GEMM; ``decode``: ``y`` is one row per sequence (a decode
         step, the last positions of a prefill), which may take the skinny
-        kernel -- with the tied embedding too."""
+        kernel -- with the tied embedding too.  A released head weight is
+        read in its packed form at any row count."""
+        if getattr(self.lm_head, "weight_packed", False):
+            return _lin_decode(y, self.lm_head)
         if decode and self.impl == "hip" and y.is_cuda:
             from ..ops import gemm
 
@@ -487,6 +537,7 @@ class Llama(nn.Module):
         Leaves ``training``, ``last_z_loss`` and every ``.grad`` alone."""
         if head_chunk is not None and head_chunk < 1:
             raise ValueError(f"head_chunk must be >= 1 or None, got {head_chunk}")
+        self._need_bf16("evaluate")
         y = self._final_hidden(tokens)
         labels = labels.reshape(-1)
         if labels.numel() != y.shape[0]:
@@ -565,9 +616,13 @@ class Llama(nn.Module):
         prompt length and for head_dim 64, nothing of the padding in the
         cache.  Each row keeps the logits of the chunk that holds its last
         real position (a device-side ``where``, no sync).  The rounding
-        differs from the unchunked path's."""
+        differs from the unchunked path's.  A model that runs from its packed
+        weights alone (``quantize_weights(keep_bf16=False)``) has no training
+        forward path: ``chunk=None`` is then one chunk of ``P`` positions."""
         B, P = tokens.shape
         c = self.cfg
+        if chunk is None and self._packed:
+            chunk = P
         if B != cache.batch or P > cache.max_len:
             raise ValueError(f"prefill: {B} x {P} prompts do not fit a {cache.batch} x {cache.max_len} cache")
         if lens is None:
@@ -705,6 +760,7 @@ class Llama(nn.Module):
 
     def forward(self, tokens: torch.Tensor, labels: torch.Tensor | None = None):
         """``tokens`` [B, S] int64 -> mean CE loss if ``labels`` given, else logits."""
+        self._need_bf16("forward")
         B, S = tokens.shape
         y = self._final_hidden(tokens)
         logits = self._head(y)

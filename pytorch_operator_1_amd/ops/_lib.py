@@ -31,12 +31,13 @@ HIPCC = os.environ.get("HIPCC", shutil.which("hipcc") or "/opt/rocm/bin/hipcc")
 HIP_SOURCES = ("kernels/mnist_kernels.hip", "kernels/common_kernels.hip", "kernels/optim_kernels.hip",
                "kernels/llm_kernels.hip", "kernels/attention.hip", "kernels/bn_kernels.hip", "kernels/conv3x3.hip",
                "kernels/conv3x3_wgrad.hip", "kernels/gemm_bf16.hip", "comm/xgmi_allreduce.hip", "kernels/decode.hip",
-               "kernels/gemm_skinny.hip", "kernels/attn_extend.hip", "kernels/gemm_skinny_mx.hip")
+               "kernels/gemm_skinny.hip", "kernels/attn_extend.hip", "kernels/gemm_skinny_mx.hip",
+               "kernels/gemm_mx.hip")
 
 _lock = threading.Lock()
 # launchers return an int hipError; these few return something else
 _RESTYPES = {"pto_ar_timeout_ticks": ctypes.c_longlong, "pto_gemm_skinny_workspace": ctypes.c_longlong,
-             "pto_gemm_skinny_mx_workspace": ctypes.c_longlong}
+             "pto_gemm_skinny_mx_workspace": ctypes.c_longlong, "pto_gemm_mx_workspace": ctypes.c_longlong}
 _lib = None
 
 
@@ -195,6 +196,12 @@ _SIGS = {
     "pto_gemm_skinny_mx_splits": [_L, _L, _I],
     "pto_gemm_skinny_mx_workspace": [_L, _L, _I],
     "pto_quant_mx": [_P, _L, _P, _P, _I, _L, _L, _P],
+    # weight-only MXFP4 / MXFP8 GEMM for any row count (csrc/kernels/gemm_mx.hip):
+    # x, lda, data, scales, out, ldc, out_f32, epilogue, fmt, M, N, K, n_splits, workspace, workspace bytes, stream
+    "pto_gemm_mx": [_P, _L, _P, _P, _P, _L, _I, _I, _I, _L, _L, _L, _I, _P, _L, _P],
+    "pto_gemm_mx_supported": [_I, _I, _L, _L, _L],
+    "pto_gemm_mx_splits": [_L, _L, _L, _I],
+    "pto_gemm_mx_workspace": [_L, _L, _I],
     "pto_maxpool_fwd": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P],
     "pto_stem_fwd": [_P, _P, _L, _L, _L, _L, _P, _P, _I, _P],
     "pto_maxpool_bwd": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P],

@@ -510,6 +510,109 @@ def skinny_mx_nt(x, q: MXWeight, out=None, out_dtype=None, swiglu: bool = False,
     return out
 
 
+# ---------------------------------------------------------------- MX weight-only GEMM for any row count
+# csrc/kernels/gemm_mx.hip: the product against a packed MX weight with no
+# limit on the rows, so that a model can run from its packed weights alone.
+
+
+def mx_takes(rows: int, n_out: int, k_in: int, swiglu: bool = False) -> bool:
+    """The MX GEMM's shape rules: any ``rows >= 1``, weight rows a multiple
+    of 32 (of 64 with ``swiglu``), contraction a multiple of 128."""
+    if rows < 1 or n_out < 1 or k_in < 1:
+        return False
+    return n_out % (64 if swiglu else 32) == 0 and k_in % 128 == 0
+
+
+def mx_splits(rows: int, n_out: int, k_in: int, fmt: str = "mxfp4") -> int:
+    """The MX GEMM's default K split across workgroups, a function of the
+    shape: small row counts with few weight rows split K to fill the device."""
+    return int(_lib.lib().pto_gemm_mx_splits(rows, n_out, k_in, MX_FORMATS[fmt]))
+
+
+def mx_nt(x, q: MXWeight, out=None, out_dtype=None, swiglu: bool = False, n_splits: int | None = None):
+    """:func:`skinny_mx_nt` with no limit on the rows: ``x[M,K] @
+    dequantize_mx(q).T`` for any ``M >= 1`` (bf16 ``x``, fp32 sums, bf16 or
+    fp32 out), the weight read in its packed form.  ``swiglu``: bitwise
+    :func:`..ops.llm.swiglu` of the plain bf16 result with the same
+    ``n_splits`` (default :func:`mx_splits`).  Row ``m`` of the result depends
+    on ``x[m]``, ``q`` and ``n_splits`` only.  HIP tensors launch the kernel
+    and raise on a refused shape; CPU tensors compute against
+    ``dequantize_mx(q)``."""
+    if not isinstance(q, MXWeight):
+        raise TypeError(f"mx_nt: q must be an MXWeight, not {type(q).__name__}")
+    if x.dim() != 2 or x.shape[1] != q.shape[1]:
+        raise ValueError(f"mx_nt: operand shapes {tuple(x.shape)} and {q.shape} do not match")
+    (M, K), N = x.shape, q.shape[0]
+    if swiglu and N % 2:
+        raise ValueError(f"mx_nt: swiglu needs an even number of weight rows, got {N}")
+    oshape = (M, N // 2) if swiglu else (M, N)
+    if out is not None:
+        if tuple(out.shape) != oshape or out.device != x.device:
+            raise ValueError(f"mx_nt: out must be {oshape} on {x.device}")
+        if out_dtype is not None and out_dtype != out.dtype:
+            raise ValueError(f"mx_nt: out_dtype {out_dtype} != out.dtype {out.dtype}")
+        out_dtype = out.dtype
+    if not x.is_cuda:
+        return skinny_nt(x, dequantize_mx(q, x.dtype), out=out, out_dtype=out_dtype, swiglu=swiglu)
+    if x.dtype != torch.bfloat16 or q.device != x.device:
+        raise TypeError(f"mx_nt: bf16 x and the weight on one HIP device required (got {x.dtype} on {x.device}, "
+                        f"weight on {q.device})")
+    out_dtype = out_dtype or torch.bfloat16
+    if out_dtype not in (torch.bfloat16, torch.float32) or (swiglu and out_dtype != torch.bfloat16):
+        raise TypeError(f"mx_nt: output must be bf16{'' if swiglu else ' or fp32'}, not {out_dtype}")
+    if out is None:
+        out = torch.empty(oshape, device=x.device, dtype=out_dtype)
+    for t, what in ((x, "x"), (out, "out")):
+        if t.stride(1) != 1:
+            raise RuntimeError(f"mx_nt: {what} must have unit inner stride (strides {t.stride()})")
+    lda, ldc = (t.stride(0) if t.shape[0] > 1 else t.shape[1] for t in (x, out))
+    L = _lib.lib()
+    fmt = MX_FORMATS[q.fmt]
+    ns = int(L.pto_gemm_mx_splits(M, N, K, fmt)) if n_splits is None else int(n_splits)
+    nbytes = L.pto_gemm_mx_workspace(M, N, ns) if ns > 1 else 0
+    ws = _skinny_workspace(x.device, nbytes) if nbytes > 0 else None
+    rc = L.pto_gemm_mx(x.data_ptr(), lda, q.data.data_ptr(), q.scales.data_ptr(), out.data_ptr(), ldc,
+                       int(out_dtype == torch.float32), int(bool(swiglu)), fmt, M, N, K, ns, _lib.ptr(ws),
+                       nbytes if ws is not None else 0, _lib.stream_ptr(x.device))
+    if rc == -1:
+        raise RuntimeError(f"mx_nt: unsupported shape or layout: x {tuple(x.shape)} strides {x.stride()}, {q.fmt} "
+                           f"weight {q.shape}, out strides {out.stride()}, n_splits {ns} (weight rows a multiple of "
+                           "32 (64 with swiglu), contraction a multiple of 128, row strides multiples of 8, 16-byte "
+                           "aligned pointers, 1..64 splits)")
+    _lib.check(rc, "mx_nt")
+    return out
+
+
+def linear_mx(x, q: MXWeight, swiglu: bool = False):
+    """The bias-free linear layer ``x [..., k_in]`` against the packed weight
+    ``q`` alone (no bf16 copy of it is read), with ``swiglu`` the SwiGLU of a
+    fused gate|up weight applied to it.  bf16 HIP tensors go by row count: up
+    to :data:`SKINNY_MAX_ROWS` rows :func:`skinny_mx_nt` where it takes the
+    shape, otherwise :func:`mx_nt`.  CPU tensors, other dtypes and shapes both
+    kernels refuse dequantise ``q`` and call ``F.linear`` (and
+    :func:`..ops.llm.swiglu`)."""
+    n_out, k_in = q.shape
+    rows = x.numel() // max(x.shape[-1], 1)
+    if x.is_cuda and x.dtype == torch.bfloat16 and q.device == x.device and x.shape[-1] == k_in and rows >= 1:
+        fn = None
+        if skinny_mx_takes(rows, n_out, k_in, swiglu):
+            fn = skinny_mx_nt
+        elif mx_takes(rows, n_out, k_in, swiglu):
+            fn = mx_nt
+        if fn is not None:
+            y = fn(_rows(x), q, swiglu=swiglu)
+            return y.view(*x.shape[:-1], y.shape[-1])
+    y = F.linear(x, dequantize_mx(q, x.dtype))
+    if swiglu and y.is_cuda and y.dtype == torch.bfloat16:
+        from . import llm
+
+        y = llm.swiglu(y)
+    elif swiglu:  # llm.swiglu's arithmetic in torch, as skinny_nt's CPU path
+        g, u = y.float().chunk(2, dim=-1)
+        y = ((g * torch.sigmoid(g)).to(x.dtype).float() * u).to(x.dtype)
+    return y
+
+
 def linear_decode(x, w, swiglu: bool = False, mx: MXWeight | None = None):
     """The bias-free linear layer of a decode step, ``x [B, k_in]`` against
     ``w [n_out, k_in]``, with ``swiglu`` the SwiGLU of a fused gate|up weight

@@ -47,9 +47,21 @@ step of ``Llama.generate`` at B in {1, 8} on bf16 weights (``PTO_SKINNY`` 0
 and 1) and after ``quantize_weights`` of each format; and, for information,
 the logits of the quantised llama3-mini against its unquantised self.
 
+``--part mxrows`` (profiles/gemm_mx_rows.md): the any-row MX GEMM
+(``ops.gemm.mx_nt``) on the layer shapes of llama3-1b and llama3-8b at M in
+{32, 64, 128, 512, 2048}, both formats (w13 also with the SwiGLU epilogue),
+against ``F.linear`` on the dequantised bf16 weight (plus ``llm.swiglu``) and
+the package's bf16 GEMM (``ops.gemm.gemm_nt``), sides alternating and weights
+rotating as in ``--part mx``; bytes/s counts each side's own weight bytes
+once, TFLOP/s ``2 M N K``.  A coarse ``n_splits`` sweep at M = 32 for every
+shape.  Then llama3-8b end to end, ``quantize_weights(mxfp4)`` with the bf16
+weights kept against ``keep_bf16=False``: ``torch.cuda.memory_allocated()``,
+a 2048-token prefill, ``extend`` at B = 8, T = 8 and the graph-replayed decode
+step at B = 8.
+
 One JSON line per row.
 
-    python tools/decode_bench.py [--part attn|generate|linear|extend|mx|all] [--rounds 15] [--reps 20]
+    python tools/decode_bench.py [--part attn|generate|linear|extend|mx|mxrows|all] [--rounds 15] [--reps 20]
                                  [--models llama3-1b] [--prompt 512] [--new 128] [--repeats 3]
 """
 from __future__ import annotations
@@ -507,9 +519,132 @@ def mx(args):
                           "relerr": round(float((got - ref).norm() / ref.norm()), 5)}), flush=True)
 
 
+def mxrows(args):
+    """The any-row MX GEMM against the bf16 paths; a model on its packed weights alone."""
+    import torch
+    import torch.nn.functional as F
+
+    from pytorch_operator_1_amd.models.llama import CONFIGS, KVCache, Llama
+    from pytorch_operator_1_amd.ops import gemm, llm
+
+    dev = torch.device("cuda")
+    fmts = ("mxfp4", "mxfp8")
+    bits = {"mxfp4": 4.25, "mxfp8": 8.25}
+    for name in ("llama3-1b", "llama3-8b"):
+        for layer, n_out, k_in in linear_shapes(CONFIGS[name]):
+            w_bytes = n_out * k_in * 2
+            qbytes = {f: int(n_out * k_in * bits[f] / 8) for f in fmts}
+            g = torch.Generator(device=dev).manual_seed(0)
+            w0 = torch.randn(n_out, k_in, device=dev, dtype=torch.bfloat16, generator=g) * k_in ** -0.5
+            pools = {}
+            for f in fmts:  # each side rotates over at least LLC_BYTES of its own bytes; the values repeat
+                q = gemm.quantize_mx(w0, f)
+                pools[f] = [q] + [gemm.MXWeight(q.data.clone(), q.scales.clone(), f, q.shape)
+                                  for _ in range(max(2, -(-LLC_BYTES // qbytes[f])) - 1)]
+            wd = gemm.dequantize_mx(pools["mxfp4"][0])
+            pools["bf16"] = [wd] + [wd.clone() for _ in range(max(2, -(-LLC_BYTES // w_bytes)) - 1)]
+            del w0
+            turn = {k: 0 for k in pools}
+
+            def nxt(kind):
+                turn[kind] = (turn[kind] + 1) % len(pools[kind])
+                return pools[kind][turn[kind]]
+
+            def row(case, med, mn, nbytes, M, **kw):
+                print(json.dumps({"part": "mxrows", "model": name, "layer": layer, "n_out": n_out, "k_in": k_in, "M": M,
+                                  **kw, "case": case, "weight_MB": round(nbytes / 2**20, 1), "rounds": args.rounds,
+                                  "reps": args.reps, "median_us": round(med, 2), "min_us": round(mn, 2),
+                                  "TBps_median": round(nbytes / med / 1e6, 3),
+                                  "fraction_of_ceiling": round(nbytes / (med * 1e-6) / CEILING, 3),
+                                  "TFLOPs_median": round(2 * M * n_out * k_in / med / 1e6, 1)}), flush=True)
+
+            for M in (32, 64, 128, 512, 2048):
+                x = torch.randn(M, k_in, device=dev, dtype=torch.bfloat16, generator=g)
+                sides = [(f"mx_nt {f}", (lambda f=f: gemm.mx_nt(x, nxt(f))), qbytes[f], gemm.mx_splits(M, n_out, k_in, f))
+                         for f in fmts]
+                sides += [("F.linear", lambda: F.linear(x, nxt("bf16")), w_bytes, None),
+                          ("gemm_nt", lambda: gemm.gemm_nt(x, nxt("bf16")), w_bytes, None)]
+                if layer == "w13":
+                    sides += [(f"mx_nt {f} swiglu", (lambda f=f: gemm.mx_nt(x, nxt(f), swiglu=True)), qbytes[f],
+                               gemm.mx_splits(M, n_out, k_in, f)) for f in fmts]
+                    sides += [("F.linear + llm.swiglu", lambda: llm.swiglu(F.linear(x, nxt("bf16"))), w_bytes, None)]
+                res = timed_pair([s[1] for s in sides], args.rounds, args.reps)
+                for (case, _, nbytes, ns), (med, mn) in zip(sides, res):
+                    row(case, med, mn, nbytes, M, n_splits=ns)
+            x = torch.randn(32, k_in, device=dev, dtype=torch.bfloat16, generator=g)
+            sweep = [n for n in (1, 2, 4, 8, 16) if n <= max(1, k_in // 256)]
+            res = timed_pair([lambda n=n: gemm.mx_nt(x, nxt("mxfp4"), n_splits=n) for n in sweep], args.rounds,
+                             args.reps)
+            for n, (med, mn) in zip(sweep, res):
+                row("mx_nt mxfp4, n_splits sweep", med, mn, qbytes["mxfp4"], 32, n_splits=n,
+                    default=gemm.mx_splits(32, n_out, k_in, "mxfp4"))
+            del pools, wd
+            torch.cuda.empty_cache()
+
+    # llama3-8b end to end: the bf16 weights kept next to the packed ones, then released
+    name, B = "llama3-8b", 8
+    torch.manual_seed(0)
+    model = Llama(CONFIGS[name], impl="hip", device=dev)
+    cfg = model.cfg
+    gen = torch.Generator(device=dev).manual_seed(1)
+    long_prompt = torch.randint(0, cfg.vocab_size, (1, 2048), device=dev, generator=gen)
+    chunk = torch.randint(0, cfg.vocab_size, (B, 8), device=dev, generator=gen)
+    prompts = torch.randint(0, cfg.vocab_size, (B, args.prompt), device=dev, generator=gen)
+
+    def clock(fn):
+        ts = []
+        for _ in range(args.repeats + 1):  # the first run warms up
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            ts.append((time.perf_counter() - t0) * 1e3)
+        ts = sorted(ts[1:])
+        return round(ts[len(ts) // 2], 3), round(ts[0], 3)
+
+    for keep in (True, False):
+        before = torch.cuda.memory_allocated()
+        model.quantize_weights("mxfp4", keep_bf16=keep)
+        torch.cuda.synchronize()
+        base = {"part": "mxrows", "model": name, "fmt": "mxfp4", "keep_bf16": keep, "repeats": args.repeats}
+        print(json.dumps({**base, "case": "memory_allocated", "GB_before": round(before / 1e9, 2),
+                          "GB_after": round(torch.cuda.memory_allocated() / 1e9, 2)}), flush=True)
+        cache = KVCache(cfg, 1, 2048, dev)
+        med, mn = clock(lambda: model.prefill(long_prompt, None, cache))
+        print(json.dumps({**base, "case": "prefill", "B": 1, "prompt": 2048, "median_ms": med, "min_ms": mn}),
+              flush=True)
+        cache = KVCache(cfg, B, 1024, dev)
+
+        def ext():
+            cache.reset()
+            cache.lens.fill_(512)
+            model.extend(chunk, cache, logits="last")
+
+        med, mn = clock(ext)
+        print(json.dumps({**base, "case": "extend", "B": B, "T": 8, "history": 512, "median_ms": med, "min_ms": mn}),
+              flush=True)
+        del cache
+
+        def run(n_new):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            model.generate(prompts, max_new_tokens=n_new, graph=n_new > 1)
+            torch.cuda.synchronize()
+            return time.perf_counter() - t0
+
+        run(args.new)
+        run(1)
+        pre = sorted(run(1) for _ in range(args.repeats))[args.repeats // 2]
+        tot = sorted(run(args.new) for _ in range(args.repeats))
+        print(json.dumps({**base, "case": "graph-replayed decode step", "B": B, "prompt": args.prompt,
+                          "new_tokens": args.new,
+                          "decode_ms_per_step": round((tot[len(tot) // 2] - pre) / (args.new - 1) * 1e3, 4),
+                          "decode_ms_per_step_min": round((tot[0] - pre) / (args.new - 1) * 1e3, 4)}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--part", choices=["attn", "generate", "linear", "extend", "mx", "all"], default="all")
+    ap.add_argument("--part", choices=["attn", "generate", "linear", "extend", "mx", "mxrows", "all"], default="all")
     ap.add_argument("--rounds", type=int, default=15)
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--models", default="llama3-1b")
@@ -533,6 +668,8 @@ def main():
         extend(args)
     if args.part in ("mx", "all"):
         mx(args)
+    if args.part in ("mxrows", "all"):
+        mxrows(args)
 
 
 if __name__ == "__main__":

@@ -187,15 +187,16 @@ class LlamaBlock(nn.Module):
 
         c = self.cfg
         k, v = cache.k[layer], cache.v[layer]
+        ksc = cache.kv_scale[layer] if cache.kv_scale is not None else None  # an fp8 cache's scales
         if hip:
             if delta is None:
                 y = llm.rmsnorm(h, self.attn_norm, c.norm_eps)
             else:
                 h, y = llm.add_rmsnorm(h, delta, self.attn_norm, c.norm_eps)
             qkv = _lin_decode(y, self.wqkv)
-            llm.rope_kv_append(qkv, rope[0], rope[1], k, v, cache.lens, c.n_heads, c.n_kv_heads)
+            llm.rope_kv_append(qkv, rope[0], rope[1], k, v, cache.lens, c.n_heads, c.n_kv_heads, kv_scale=ksc)
             ctx = llm.attention_decode(qkv, k, v, cache.lens_incl, c.n_heads, c.n_kv_heads,
-                                       impl="sdpa" if ATTN_IMPL == "sdpa" else None)
+                                       impl="sdpa" if ATTN_IMPL == "sdpa" else None, kv_scale=ksc)
             h, y = llm.add_rmsnorm(h, _lin_decode(ctx, self.wo), self.ffn_norm, c.norm_eps)
             # on the skinny kernel the SwiGLU is w13's epilogue: no [B, 2F] round trip
             return h, _lin_decode(_lin_decode(y, self.w13, swiglu=True), self.w2)
@@ -203,8 +204,9 @@ class LlamaBlock(nn.Module):
             h = h + delta
         y = _rmsnorm_ref(h, self.attn_norm, c.norm_eps)
         qkv = F.linear(y, self.wqkv.weight)
-        llm.rope_kv_append(qkv, rope[0], rope[1], k, v, cache.lens, c.n_heads, c.n_kv_heads, impl="torch")
-        ctx = llm.attention_decode(qkv, k, v, cache.lens_incl, c.n_heads, c.n_kv_heads, impl="torch")
+        llm.rope_kv_append(qkv, rope[0], rope[1], k, v, cache.lens, c.n_heads, c.n_kv_heads, impl="torch",
+                           kv_scale=ksc)
+        ctx = llm.attention_decode(qkv, k, v, cache.lens_incl, c.n_heads, c.n_kv_heads, impl="torch", kv_scale=ksc)
         h = h + F.linear(ctx, self.wo.weight)
         y = _rmsnorm_ref(h, self.ffn_norm, c.norm_eps)
         g, u = F.linear(y, self.w13.weight).chunk(2, dim=-1)
@@ -220,23 +222,27 @@ class LlamaBlock(nn.Module):
 
         c = self.cfg
         k, v = cache.k[layer], cache.v[layer]
+        ksc = cache.kv_scale[layer] if cache.kv_scale is not None else None
         if hip:
             if delta is None:
                 y = llm.rmsnorm(h, self.attn_norm, c.norm_eps)
             else:
                 h, y = llm.add_rmsnorm(h, delta, self.attn_norm, c.norm_eps)
             qkv = _lin_rows(y, self.wqkv)
-            llm.rope_kv_extend(qkv, rope[0], rope[1], k, v, cache.lens, n_new, T, c.n_heads, c.n_kv_heads)
+            llm.rope_kv_extend(qkv, rope[0], rope[1], k, v, cache.lens, n_new, T, c.n_heads, c.n_kv_heads,
+                               kv_scale=ksc)
             ctx = llm.attention_extend(qkv, k, v, cache.lens, n_new, T, c.n_heads, c.n_kv_heads,
-                                       impl="sdpa" if ATTN_IMPL == "sdpa" else None)
+                                       impl="sdpa" if ATTN_IMPL == "sdpa" else None, kv_scale=ksc)
             h, y = llm.add_rmsnorm(h, _lin_rows(ctx, self.wo), self.ffn_norm, c.norm_eps)
             return h, _lin_rows(_lin_rows(y, self.w13, swiglu=True), self.w2)
         if delta is not None:
             h = h + delta
         y = _rmsnorm_ref(h, self.attn_norm, c.norm_eps)
         qkv = F.linear(y, self.wqkv.weight)
-        llm.rope_kv_extend(qkv, rope[0], rope[1], k, v, cache.lens, n_new, T, c.n_heads, c.n_kv_heads, impl="torch")
-        ctx = llm.attention_extend(qkv, k, v, cache.lens, n_new, T, c.n_heads, c.n_kv_heads, impl="torch")
+        llm.rope_kv_extend(qkv, rope[0], rope[1], k, v, cache.lens, n_new, T, c.n_heads, c.n_kv_heads, impl="torch",
+                           kv_scale=ksc)
+        ctx = llm.attention_extend(qkv, k, v, cache.lens, n_new, T, c.n_heads, c.n_kv_heads, impl="torch",
+                                   kv_scale=ksc)
         h = h + F.linear(ctx, self.wo.weight)
         y = _rmsnorm_ref(h, self.ffn_norm, c.norm_eps)
         g, u = F.linear(y, self.w13.weight).chunk(2, dim=-1)
@@ -249,11 +255,27 @@ class KVCache:
     head_dim]`` so one head's keys are contiguous, and the device-side
     bookkeeping -- ``lens`` int32 ``[batch]`` (keys held per row), ``step``
     int32 ``[1]`` (tokens emitted), ``done`` int32 ``[batch]`` (row has
-    emitted ``eos_id``).  Nothing past ``lens[b]`` is ever read."""
+    emitted ``eos_id``).  Nothing past ``lens[b]`` is ever read.
 
-    def __init__(self, cfg: LlamaConfig, batch: int, max_len: int, device=None, dtype=torch.bfloat16):
+    ``dtype=torch.float8_e4m3fn`` holds K and V as one e4m3 byte per element
+    with one fp32 scale per layer and KV head, ``k_scale`` / ``v_scale`` (a
+    float, or a ``[n_layers, n_kv_heads]`` tensor): a cached value means
+    ``byte * scale``.  ``kv_scale[layer]`` is then the fp32 ``[4, n_kv_heads]``
+    tensor (k_scale, v_scale, 1/k_scale, 1/v_scale) the cache ops of
+    :mod:`..ops.llm` take; for every other dtype ``kv_scale`` is None.  The
+    decode step on an fp8 cache runs on kernels of its own; chunked prefill and
+    :meth:`Llama.extend` on one are correct but slow (a torch path)."""
+
+    def __init__(self, cfg: LlamaConfig, batch: int, max_len: int, device=None, dtype=torch.bfloat16,
+                 k_scale=1.0, v_scale=1.0):
         if batch < 1 or max_len < 1:
             raise ValueError(f"KVCache: batch and max_len must be >= 1, got {batch}, {max_len}")
+        self.kv_scale = None
+        if dtype == torch.float8_e4m3fn:
+            ks, vs = (torch.as_tensor(x, dtype=torch.float32, device=device).expand(cfg.n_layers, cfg.n_kv_heads)
+                      for x in (k_scale, v_scale))
+            self.kv_scale = [torch.stack((ks[i], vs[i], 1 / ks[i], 1 / vs[i])).contiguous()
+                             for i in range(cfg.n_layers)]
         self.cfg, self.batch, self.max_len = cfg, int(batch), int(max_len)
         shape = (self.batch, cfg.n_kv_heads, self.max_len, cfg.head_dim)
         self.k = [torch.zeros(shape, device=device, dtype=dtype) for _ in range(cfg.n_layers)]
@@ -605,7 +627,7 @@ class Llama(nn.Module):
     def prefill(self, tokens: torch.Tensor, lens: torch.Tensor | None, cache: KVCache, chunk: int | None = None):
         """Run the right-padded prompts ``tokens`` [B, P] through the training
         forward path, copy every layer's rotated K and its V into ``cache``
-        and set ``cache.lens`` to ``lens`` (int32 [B] on the device; None: P
+        (quantised by the appends' rule into a ``float8_e4m3fn`` cache) and set ``cache.lens`` to ``lens`` (int32 [B] on the device; None: P
         for every row).  Returns the logits ``[B, V]`` at each row's last real
         position.  Causality keeps the padding out of every real position,
         and what the padding leaves in the cache lies past ``lens``.
@@ -643,8 +665,14 @@ class Llama(nn.Module):
         H, Hkv = c.n_heads, c.n_kv_heads
         for i, qkv in enumerate(kv):
             v4 = qkv.view(B, P, H + 2 * Hkv, c.head_dim)
-            cache.k[i][:, :, :P].copy_(v4[:, :, H:H + Hkv].transpose(1, 2))
-            cache.v[i][:, :, :P].copy_(v4[:, :, H + Hkv:].transpose(1, 2))
+            kn, vn = v4[:, :, H:H + Hkv].transpose(1, 2), v4[:, :, H + Hkv:].transpose(1, 2)
+            if cache.kv_scale is not None:  # an fp8 cache: the appends' quantising rule
+                from ..ops import llm
+
+                inv = cache.kv_scale[i][2:, None, :, None, None]
+                kn, vn = llm._quantize_kv(kn, inv[0]), llm._quantize_kv(vn, inv[1])
+            cache.k[i][:, :, :P].copy_(kn)
+            cache.v[i][:, :, :P].copy_(vn)
         cache.reset()
         cache.lens.copy_(lens)
         last = (lens.long() - 1).clamp(0, P - 1)[:, None, None].expand(B, 1, c.dim)

@@ -32,7 +32,7 @@ HIP_SOURCES = ("kernels/mnist_kernels.hip", "kernels/common_kernels.hip", "kerne
                "kernels/llm_kernels.hip", "kernels/attention.hip", "kernels/bn_kernels.hip", "kernels/conv3x3.hip",
                "kernels/conv3x3_wgrad.hip", "kernels/gemm_bf16.hip", "comm/xgmi_allreduce.hip", "kernels/decode.hip",
                "kernels/gemm_skinny.hip", "kernels/attn_extend.hip", "kernels/gemm_skinny_mx.hip",
-               "kernels/gemm_mx.hip")
+               "kernels/gemm_mx.hip", "kernels/kv_fp8.hip")
 
 _lock = threading.Lock()
 # launchers return an int hipError; these few return something else
@@ -219,6 +219,11 @@ _SIGS = {
     "pto_attn_extend_supported": [_I, _I, _I],
     "pto_attn_extend_chunk": [_I, _I],
     "pto_attn_extend": [_P, _L, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _F, _P],
+    # FP8 (e4m3) KV cache: quantising T-token append, split-KV decode attention (csrc/kernels/kv_fp8.hip):
+    # the bf16 launchers' arguments with kv_scale fp32 [4][Hkv] after the caches
+    "pto_rope_kv_extend_fp8": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P],
+    "pto_attn_decode_fp8_chunk": [_I, _I],
+    "pto_attn_decode_fp8": [_P, _L, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _P],
     # xGMI peer all-reduce (csrc/comm/xgmi_allreduce.hip)
     "pto_ar_ipc_handle_size": [],
     "pto_ar_flag_bytes": [_I],

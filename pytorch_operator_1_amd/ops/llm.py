@@ -492,7 +492,59 @@ def _i32(t, name: str, n: int):
     return t
 
 
-def rope_kv_append(qkv, cos, sin, k_cache, v_cache, lens, n_heads: int, n_kv_heads: int, impl: str | None = None):
+_FP8 = torch.float8_e4m3fn
+DECODE_KEY_TILE_FP8 = 128
+
+
+def _fp8_caches(name: str, k_cache, v_cache, kv_scale) -> bool:
+    """True for e4m3 caches, whose ``kv_scale`` (fp32 ``[4, Hkv]``: k_scale,
+    v_scale, 1/k_scale, 1/v_scale per KV head) is then required; any other
+    cache dtype takes none."""
+    fp8 = k_cache.dtype == _FP8
+    if fp8 != (v_cache.dtype == _FP8):
+        raise ValueError(f"{name}: k_cache and v_cache must share a dtype")
+    if not fp8:
+        if kv_scale is not None:
+            raise ValueError(f"{name}: kv_scale goes with float8_e4m3fn caches only")
+        return False
+    if kv_scale is None or kv_scale.dtype != torch.float32 or kv_scale.shape != (4, k_cache.shape[1]) \
+            or not kv_scale.is_contiguous() or kv_scale.device != k_cache.device:
+        raise ValueError(f"{name}: float8_e4m3fn caches need kv_scale, contiguous fp32 [4, Hkv] on the caches' device")
+    return True
+
+
+def _dequantize_kv(k_cache, v_cache, kv_scale):
+    """fp32 ``bytes * scale`` of both caches (the bytes past the valid prefix
+    may be NaN: the callers discard them)."""
+    return k_cache.float() * kv_scale[0][None, :, None, None], v_cache.float() * kv_scale[1][None, :, None, None]
+
+
+def _quantize_kv(x, inv_scale):
+    """The cache's quantising rule: ``e4m3_rne(clamp(float(x) * inv_scale,
+    -448, 448))`` (clamped first, so no convert ever overflows).  NaN / inf
+    inputs: unspecified."""
+    return (x.float() * inv_scale).clamp(-448, 448).to(_FP8)
+
+
+def _rope_kv_fp8_hip(name: str, qkv, cos, sin, k_cache, v_cache, kv_scale, lens, n_new, T: int, H: int) -> bool:
+    """Launch the quantising append (csrc/kernels/kv_fp8.hip) where it applies:
+    bf16 ``qkv`` on the device, contiguous caches, ``D % 16 == 0``."""
+    _, Hkv, max_len, D = k_cache.shape
+    if not (_hip_bf16(qkv) and k_cache.is_cuda and D % 16 == 0 and k_cache.is_contiguous()
+            and v_cache.is_contiguous()):
+        return False
+    cos, sin = cos.contiguous(), sin.contiguous()
+    if cos.dtype != torch.float32 or sin.dtype != torch.float32:
+        raise TypeError(f"{name}: fp32 cos/sin tables required")
+    _lib.check(_lib.lib().pto_rope_kv_extend_fp8(qkv.data_ptr(), cos.data_ptr(), sin.data_ptr(), k_cache.data_ptr(),
+                                                 v_cache.data_ptr(), kv_scale.data_ptr(), lens.data_ptr(), _p(n_new),
+                                                 k_cache.shape[0], T, H, Hkv, D, max_len, cos.shape[0],
+                                                 _lib.stream_ptr(qkv.device)), name)
+    return True
+
+
+def rope_kv_append(qkv, cos, sin, k_cache, v_cache, lens, n_heads: int, n_kv_heads: int, impl: str | None = None,
+                   kv_scale=None):
     """Append the new token of every batch row to the KV cache.
 
     ``qkv`` ``[B, (H + 2*Hkv)*D]`` is the fused QKV projection of ONE new
@@ -503,16 +555,27 @@ def rope_kv_append(qkv, cos, sin, k_cache, v_cache, lens, n_heads: int, n_kv_hea
     ``[B, Hkv, max_len, D]``).  The arithmetic is :func:`rope_`'s, so the
     appended key is bitwise the key prefill produces at that position.  A row
     with ``p >= max_len`` or ``p`` at or past the table length is left alone
-    entirely.  Returns ``qkv``."""
+    entirely.  Returns ``qkv``.
+
+    ``torch.float8_e4m3fn`` caches take ``kv_scale`` (fp32 ``[4, Hkv]``: rows
+    k_scale, v_scale, 1/k_scale, 1/v_scale; a ValueError with any other cache
+    dtype): the rotated K head, rounded to ``qkv``'s dtype as above, and the V
+    head are stored as ``e4m3_rne(clamp(float(x) * inv_scale, -448, 448))``,
+    the quantisation of the key prefill produces.  NaN / inf inputs:
+    unspecified."""
     B, Hkv, max_len, D = k_cache.shape
     H = int(n_heads)
     if Hkv != n_kv_heads or v_cache.shape != k_cache.shape:
         raise ValueError("rope_kv_append: caches must both be [B, Hkv, max_len, D]")
+    fp8 = _fp8_caches("rope_kv_append", k_cache, v_cache, kv_scale)
     if qkv.shape != (B, (H + 2 * Hkv) * D) or not qkv.is_contiguous():
         raise ValueError(f"rope_kv_append: qkv must be contiguous [B, (H + 2*Hkv)*D], got {tuple(qkv.shape)}")
     if cos.shape != sin.shape or cos.shape[-1] != D // 2:
         raise ValueError("rope_kv_append: cos/sin must be [positions, D/2]")
     _i32(lens, "rope_kv_append: lens", B)
+    if fp8 and impl != "torch" and _rope_kv_fp8_hip("rope_kv_append", qkv, cos, sin, k_cache, v_cache, kv_scale, lens,
+                                                    None, 1, H):
+        return qkv
     if impl != "torch" and _hip_bf16(qkv, k_cache, v_cache) and D % 8 == 0 and k_cache.is_contiguous() \
             and v_cache.is_contiguous():
         cos, sin = cos.contiguous(), sin.contiguous()
@@ -532,7 +595,9 @@ def rope_kv_append(qkv, cos, sin, k_cache, v_cache, lens, n_heads: int, n_kv_hea
     rot = (rot * c + _rotate_half(rot) * s).to(qkv.dtype)
     v3[:, :H] = torch.where(ok, rot[:, :H], v3[:, :H])
     idx = p[:, None, None, None].expand(B, Hkv, 1, D)
-    for cache, new in ((k_cache, rot[:, H:]), (v_cache, v3[:, H + Hkv:])):
+    for row, (cache, new) in enumerate(((k_cache, rot[:, H:]), (v_cache, v3[:, H + Hkv:]))):
+        if fp8:  # scatter the bytes
+            cache, new = cache.view(torch.uint8), _quantize_kv(new, kv_scale[2 + row][None, :, None]).view(torch.uint8)
         cache.scatter_(2, idx, torch.where(ok, new.to(cache.dtype), cache.gather(2, idx)[:, :, 0])[:, :, None])
     return qkv
 
@@ -553,14 +618,16 @@ def decode_splits(B: int, Hkv: int, max_len: int) -> int:
     return max(1, min(by_len, by_cus))
 
 
-def decode_chunk(max_len: int, n_splits: int) -> int:
-    """Keys per split: ``ceil(max_len / n_splits)`` rounded up to the key tile."""
+def decode_chunk(max_len: int, n_splits: int, fp8: bool = False) -> int:
+    """Keys per split: ``ceil(max_len / n_splits)`` rounded up to the key tile
+    (64 keys; 128 on a ``float8_e4m3fn`` cache)."""
     c = -(-int(max_len) // int(n_splits))
-    return -(-c // DECODE_KEY_TILE) * DECODE_KEY_TILE
+    tile = DECODE_KEY_TILE_FP8 if fp8 else DECODE_KEY_TILE
+    return -(-c // tile) * tile
 
 
 def attention_decode(q, k_cache, v_cache, lens, n_heads: int, n_kv_heads: int, n_splits: int | None = None,
-                     impl: str | None = None):
+                     impl: str | None = None, kv_scale=None):
     """One query row per head against the cached history: ``O [B, H*D]``.
 
     ``q`` holds the (rotated) query heads of the new token in its first
@@ -573,11 +640,18 @@ def attention_decode(q, k_cache, v_cache, lens, n_heads: int, n_kv_heads: int, n
     softmaxes in split order; the output bits depend on ``(inputs, lens,
     max_len, n_splits)`` only.  ``impl="sdpa"`` / ``"torch"``, CPU tensors
     and shapes outside :func:`attention_decode_supported` use torch's SDPA
-    over the valid prefix."""
+    over the valid prefix.
+
+    ``torch.float8_e4m3fn`` caches take ``kv_scale`` (fp32 ``[4, Hkv]``, see
+    :func:`rope_kv_append`) and mean ``bytes * k_scale`` / ``bytes *
+    v_scale``.  They run on the kernel of csrc/kernels/kv_fp8.hip, whose key
+    tile is 128 (``decode_chunk(..., fp8=True)``); the fallback dequantises
+    the valid prefix and goes on as above."""
     B, Hkv, max_len, D = k_cache.shape
     H = int(n_heads)
     if Hkv != n_kv_heads or v_cache.shape != k_cache.shape or H % Hkv:
         raise ValueError("attention_decode: caches must both be [B, Hkv, max_len, D] with H % Hkv == 0")
+    fp8 = _fp8_caches("attention_decode", k_cache, v_cache, kv_scale)
     if q.dim() != 2 or q.shape[0] != B or q.shape[1] < H * D or q.stride(1) != 1:
         raise ValueError(f"attention_decode: q must be [B, >= H*D] with unit inner stride, got {tuple(q.shape)}")
     _i32(lens, "attention_decode: lens", B)
@@ -585,8 +659,8 @@ def attention_decode(q, k_cache, v_cache, lens, n_heads: int, n_kv_heads: int, n
         raise ValueError(f"attention_decode: n_splits must be an integer >= 1, got {n_splits}")
     if impl not in (None, "hip", "sdpa", "torch"):
         raise ValueError(f"attention_decode: impl must be hip|sdpa|torch, got {impl!r}")
-    if impl in (None, "hip") and _hip_bf16(q, k_cache, v_cache) and attention_decode_supported(H, Hkv, D) \
-            and k_cache.is_contiguous() and v_cache.is_contiguous():
+    if impl in (None, "hip") and _hip_bf16(q, *(() if fp8 else (k_cache, v_cache))) and k_cache.is_cuda \
+            and attention_decode_supported(H, Hkv, D) and k_cache.is_contiguous() and v_cache.is_contiguous():
         if q.stride(0) % 8 or q.data_ptr() % 16:
             q = q[:, :H * D].contiguous()
         ns = decode_splits(B, Hkv, max_len) if n_splits is None else int(n_splits)
@@ -595,10 +669,18 @@ def attention_decode(q, k_cache, v_cache, lens, n_heads: int, n_kv_heads: int, n
         if ns > 1:
             ml = torch.empty(B, H, ns, 2, device=q.device, dtype=torch.float32)
             po = torch.empty(B, H, ns, D, device=q.device, dtype=torch.float32)
+        if fp8:
+            _lib.check(_lib.lib().pto_attn_decode_fp8(q.data_ptr(), q.stride(0), k_cache.data_ptr(),
+                                                      v_cache.data_ptr(), kv_scale.data_ptr(), lens.data_ptr(),
+                                                      o.data_ptr(), _p(ml), _p(po), B, H, Hkv, D, max_len, ns,
+                                                      D ** -0.5, _lib.stream_ptr(q.device)), "attn_decode_fp8")
+            return o
         _lib.check(_lib.lib().pto_attn_decode(q.data_ptr(), q.stride(0), k_cache.data_ptr(), v_cache.data_ptr(),
                                               lens.data_ptr(), o.data_ptr(), _p(ml), _p(po), B, H, Hkv, D, max_len, ns,
                                               D ** -0.5, _lib.stream_ptr(q.device)), "attn_decode")
         return o
+    if fp8:
+        k_cache, v_cache = _dequantize_kv(k_cache, v_cache, kv_scale)
     valid = (torch.arange(max_len, device=q.device)[None, :] < lens[:, None])[:, None, :, None]  # [B, 1, max_len, 1]
     zero = torch.zeros((), device=q.device, dtype=k_cache.dtype)
     k = torch.where(valid, k_cache, zero)  # whatever the tail holds is discarded, never multiplied
@@ -724,7 +806,7 @@ def _live(lens, n_new, T: int, limit: int):
 
 
 def rope_kv_extend(qkv, cos, sin, k_cache, v_cache, lens, n_new, T: int, n_heads: int, n_kv_heads: int,
-                   impl: str | None = None):
+                   impl: str | None = None, kv_scale=None):
     """Append ``T`` new tokens per batch row to the KV cache.
 
     ``qkv`` ``[B*T, (H + 2*Hkv)*D]`` is the fused QKV projection of the new
@@ -736,11 +818,14 @@ def rope_kv_extend(qkv, cos, sin, k_cache, v_cache, lens, n_new, T: int, n_heads
     head and the V head go to ``k_cache[b, :, p]`` / ``v_cache[b, :, p]``, with
     :func:`rope_`'s arithmetic: bitwise the key prefill produces there.  A
     token that is not live writes nothing and its row is left alone.  Returns
-    ``qkv``; ``lens`` is not advanced."""
+    ``qkv``; ``lens`` is not advanced.  ``torch.float8_e4m3fn`` caches take
+    ``kv_scale`` and store quantised K / V exactly as :func:`rope_kv_append`
+    does (its ``T = 1`` case)."""
     B, Hkv, max_len, D = k_cache.shape
     H, T = int(n_heads), int(T)
     if Hkv != n_kv_heads or v_cache.shape != k_cache.shape:
         raise ValueError("rope_kv_extend: caches must both be [B, Hkv, max_len, D]")
+    fp8 = _fp8_caches("rope_kv_extend", k_cache, v_cache, kv_scale)
     if T < 1 or T > max_len:
         raise ValueError(f"rope_kv_extend: T must be in [1, max_len = {max_len}], got {T}")
     if qkv.shape != (B * T, (H + 2 * Hkv) * D) or not qkv.is_contiguous():
@@ -749,6 +834,9 @@ def rope_kv_extend(qkv, cos, sin, k_cache, v_cache, lens, n_new, T: int, n_heads
         raise ValueError("rope_kv_extend: cos/sin must be [positions, D/2]")
     _i32(lens, "rope_kv_extend: lens", B)
     _i32(n_new, "rope_kv_extend: n_new", B)
+    if fp8 and impl != "torch" and _rope_kv_fp8_hip("rope_kv_extend", qkv, cos, sin, k_cache, v_cache, kv_scale, lens,
+                                                    n_new, T, H):
+        return qkv
     if impl != "torch" and _hip_bf16(qkv, k_cache, v_cache) and D % 8 == 0 and k_cache.is_contiguous() \
             and v_cache.is_contiguous():
         cos, sin = cos.contiguous(), sin.contiguous()
@@ -773,7 +861,9 @@ def rope_kv_extend(qkv, cos, sin, k_cache, v_cache, lens, n_new, T: int, n_heads
     # which gets back what it held: one scatter without duplicate indices and without a host sync
     idx = torch.remainder(pos, max_len)[:, None, :, None].expand(B, Hkv, T, D)
     okc = live[:, None, :, None]
-    for cache, new in ((k_cache, rot[:, :, H:]), (v_cache, v4[:, :, H + Hkv:])):
+    for row, (cache, new) in enumerate(((k_cache, rot[:, :, H:]), (v_cache, v4[:, :, H + Hkv:]))):
+        if fp8:  # scatter the bytes
+            cache, new = cache.view(torch.uint8), _quantize_kv(new, kv_scale[2 + row][None, None, :, None]).view(torch.uint8)
         cache.scatter_(2, idx, torch.where(okc, new.transpose(1, 2).to(cache.dtype), cache.gather(2, idx)))
     return qkv
 
@@ -790,7 +880,7 @@ def extend_row_tiles(T: int, H: int, Hkv: int) -> int:
 
 
 def attention_extend(q, k_cache, v_cache, lens, n_new, T: int, n_heads: int, n_kv_heads: int,
-                     n_splits: int | None = None, impl: str | None = None):
+                     n_splits: int | None = None, impl: str | None = None, kv_scale=None):
     """``T`` new query tokens per row against the cache: ``O [B*T, H*D]``.
 
     Runs AFTER :func:`rope_kv_extend` with the same ``lens`` / ``n_new``, so it
@@ -808,11 +898,17 @@ def attention_extend(q, k_cache, v_cache, lens, n_new, T: int, n_heads: int, n_k
     ``B``; that choice is NOT measured (profiles/extend.md).
     ``impl="sdpa"`` / ``"torch"``, CPU tensors and shapes outside
     :func:`attention_extend_supported` use torch's SDPA with a mask built from
-    the device lengths."""
+    the device lengths.
+
+    ``torch.float8_e4m3fn`` caches take ``kv_scale`` as :func:`attention_decode`
+    does and ALWAYS use the torch path on the dequantised cache: correct but
+    slow (chunked prefill and follow-up turns on an fp8 cache); an MFMA extend
+    kernel over fp8 keys does not exist yet."""
     B, Hkv, max_len, D = k_cache.shape
     H, T = int(n_heads), int(T)
     if Hkv != n_kv_heads or v_cache.shape != k_cache.shape or H % Hkv:
         raise ValueError("attention_extend: caches must both be [B, Hkv, max_len, D] with H % Hkv == 0")
+    fp8 = _fp8_caches("attention_extend", k_cache, v_cache, kv_scale)
     if T < 1 or T > max_len:
         raise ValueError(f"attention_extend: T must be in [1, max_len = {max_len}], got {T}")
     if q.dim() != 2 or q.shape[0] != B * T or q.shape[1] < H * D or q.stride(1) != 1:
@@ -838,6 +934,8 @@ def attention_extend(q, k_cache, v_cache, lens, n_new, T: int, n_heads: int, n_k
                                               lens.data_ptr(), n_new.data_ptr(), o.data_ptr(), _p(ml), _p(po), B, T, H,
                                               Hkv, D, max_len, ns, D ** -0.5, _lib.stream_ptr(q.device)), "attn_extend")
         return o
+    if fp8:
+        k_cache, v_cache = _dequantize_kv(k_cache, v_cache, kv_scale)
     pos, live = _live(lens, n_new, T, max_len)
     keys = torch.arange(max_len, device=q.device)[None, None, :]
     mask = (live[:, :, None] & (keys <= pos[:, :, None]))[:, None]  # [B, 1, T, max_len]

@@ -59,9 +59,17 @@ weights kept against ``keep_bf16=False``: ``torch.cuda.memory_allocated()``,
 a 2048-token prefill, ``extend`` at B = 8, T = 8 and the graph-replayed decode
 step at B = 8.
 
+``--part kvfp8`` (profiles/decode_kv_fp8.md): ``attention_decode`` on a bf16
+against a ``float8_e4m3fn`` cache at the (B, history) rows of ``--part attn``,
+measured alternately, each side rotating over its own cache copies, bytes/s on
+its own cache bytes; the fp8 side also at half and twice the default split
+count.  Then the llama3-mini logits on an fp8 against a bf16 cache, and the
+graph-replayed llama3-8b MXFP4 step at B = 8 on a 32768-token history with
+``torch.cuda.memory_allocated`` per cache dtype.
+
 One JSON line per row.
 
-    python tools/decode_bench.py [--part attn|generate|linear|extend|mx|mxrows|all] [--rounds 15] [--reps 20]
+    python tools/decode_bench.py [--part attn|generate|linear|extend|mx|mxrows|kvfp8|all] [--rounds 15] [--reps 20]
                                  [--models llama3-1b] [--prompt 512] [--new 128] [--repeats 3]
 """
 from __future__ import annotations
@@ -642,9 +650,112 @@ def mxrows(args):
                           "decode_ms_per_step_min": round((tot[0] - pre) / (args.new - 1) * 1e3, 4)}), flush=True)
 
 
+def kvfp8(args):
+    import torch
+
+    from pytorch_operator_1_amd.models.llama import CONFIGS, KVCache, Llama
+    from pytorch_operator_1_amd.ops import llm
+
+    dev = torch.device("cuda")
+    fp8 = torch.float8_e4m3fn
+    sc = torch.tensor([[0.5], [0.25], [2.0], [4.0]], device=dev).expand(4, HKV).contiguous()
+    for B in (1, 8):
+        for hist in (1024, 8192, 32768):
+            nbytes = {"bf16": 2 * B * HKV * hist * D * 2, "fp8": 2 * B * HKV * hist * D}
+            ncopy = max(2, -(-LLC_BYTES // nbytes["fp8"]))  # both sides rotate over at least the LLC bound
+            g = torch.Generator(device=dev).manual_seed(0)
+            pool = {"bf16": [], "fp8": []}
+            for _ in range(ncopy):
+                kv = [torch.randn(B, HKV, hist, D, device=dev, dtype=torch.bfloat16, generator=g) for _ in range(2)]
+                pool["bf16"].append(kv)
+                pool["fp8"].append([llm._quantize_kv(t, sc[2 + i, 0]) for i, t in enumerate(kv)])
+            q = torch.randn(B, H * D, device=dev, dtype=torch.bfloat16, generator=g)
+            lens = torch.full((B,), hist, device=dev, dtype=torch.int32)
+            turn = {"bf16": 0, "fp8": 0}
+
+            def run(side, ns=None):
+                turn[side] = (turn[side] + 1) % ncopy
+                k, v = pool[side][turn[side]]
+                return llm.attention_decode(q, k, v, lens, H, HKV, n_splits=ns, kv_scale=sc if side == "fp8" else None)
+
+            turn.update(bf16=0, fp8=0)
+            a, b = run("bf16").float(), run("fp8").float()
+            default = llm.decode_splits(B, HKV, hist)
+            sweep = sorted({max(1, default // 2), default, min(2 * default, max(1, hist // 128))})
+            fns = [("bf16", default), *(("fp8", ns) for ns in sweep)]
+            res = timed_pair([lambda s=s, ns=ns: run(s, ns) for s, ns in fns], args.rounds, args.reps)
+            for (side, ns), (med, mn) in zip(fns, res):
+                print(json.dumps({"part": "kvfp8", "case": f"attention_decode {side}", "B": B, "history": hist,
+                                  "cache_copies": ncopy, "kv_MB": round(nbytes[side] / 2**20, 1), "n_splits": ns,
+                                  "default_splits": default, "rounds": args.rounds, "reps": args.reps,
+                                  "median_us": round(med, 2), "min_us": round(mn, 2),
+                                  "TBps_median": round(nbytes[side] / med / 1e6, 3),
+                                  "fraction_of_ceiling": round(nbytes[side] / (med * 1e-6) / CEILING, 3),
+                                  "relerr_fp8_vs_bf16_cache": round(float((b - a).norm() / a.norm()), 5)}), flush=True)
+            del pool
+            torch.cuda.empty_cache()
+
+    # llama3-mini: what the 8-bit cache does to the logits at scale 1 (a measurement, asserted nowhere).  Token 0 comes
+    # from the prefill alone, so both runs feed the same token to step 1: its logits differ by the cache alone.
+    torch.manual_seed(0)
+    mini = Llama(CONFIGS["llama3-mini"], impl="hip", device=dev)
+    prompts = torch.randint(0, mini.cfg.vocab_size, (3, 128), device=dev,
+                            generator=torch.Generator(device=dev).manual_seed(1))
+    zs = [mini.generate(prompts, [5, 128, 37], max_new_tokens=2, return_logits=True,
+                        cache=KVCache(mini.cfg, 3, 130, dev, dt))[1][:, 1].float() for dt in (torch.bfloat16, fp8)]
+    print(json.dumps({"part": "kvfp8", "case": "llama3-mini step-1 logits, fp8 cache vs bf16 cache (scale 1)",
+                      "max_abs": round(float((zs[1] - zs[0]).abs().max()), 4),
+                      "max_abs_logit": round(float(zs[0].abs().max()), 3),
+                      "relerr": round(float((zs[1] - zs[0]).norm() / zs[0].norm()), 5)}), flush=True)
+    del mini
+
+    # llama3-8b, MXFP4 weights, B = 8 on a 32768-token history: the graph-replayed step per cache dtype.  The
+    # history is random bytes (a step's time does not depend on the values), lens is put back before every round.
+    name, B, hist = "llama3-8b", 8, 32768
+    torch.manual_seed(0)
+    model = Llama(CONFIGS[name], impl="hip", device=dev)
+    model.quantize_weights("mxfp4", keep_bf16=False)
+    cur = torch.zeros(B, device=dev, dtype=torch.int64)
+    for dt in (torch.bfloat16, fp8):
+        torch.cuda.empty_cache()
+        before = torch.cuda.memory_allocated()
+        cache = KVCache(model.cfg, B, hist, dev, dt)
+        for t in cache.k + cache.v:
+            t.normal_() if dt == torch.bfloat16 else t.view(torch.uint8).random_(0, 0x78)
+        held = torch.cuda.memory_allocated()
+
+        def one():
+            llm.sample(model.decode_step(cur, cache), cur=cur, step=cache.step, done=cache.done, lens=cache.lens,
+                       advance=True)
+
+        cache.lens.fill_(hist - args.reps)
+        one()
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph):
+            one()
+        ts = []
+        for _ in range(args.rounds + 1):  # the first round warms up
+            cache.lens.fill_(hist - args.reps)
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            for _ in range(args.reps):
+                graph.replay()
+            b.record()
+            b.synchronize()
+            ts.append(a.elapsed_time(b) / args.reps)
+        ts = sorted(ts[1:])
+        print(json.dumps({"part": "kvfp8", "case": "graph-replayed decode step", "model": name, "weights": "mxfp4",
+                          "B": B, "history": hist, "cache": str(dt).split(".")[-1], "rounds": args.rounds, "reps": args.reps,
+                          "median_ms": round(ts[len(ts) // 2], 4), "min_ms": round(ts[0], 4),
+                          "cache_GB": round((held - before) / 1e9, 2),
+                          "memory_allocated_GB": round(held / 1e9, 2)}), flush=True)
+        del graph, cache
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--part", choices=["attn", "generate", "linear", "extend", "mx", "mxrows", "all"], default="all")
+    ap.add_argument("--part", choices=["attn", "generate", "linear", "extend", "mx", "mxrows", "kvfp8", "all"],
+                    default="all")
     ap.add_argument("--rounds", type=int, default=15)
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--models", default="llama3-1b")
@@ -670,6 +781,8 @@ def main():
         mx(args)
     if args.part in ("mxrows", "all"):
         mxrows(args)
+    if args.part in ("kvfp8", "all"):
+        kvfp8(args)
 
 
 if __name__ == "__main__":
